@@ -6,9 +6,13 @@ synapse matrix resident in HBM before the timed region.  `--gpus N` > 1 (launche
 rank per GPU) shards the SAME lattice by postsynaptic population (strong scaling) with one RCCL
 all-gather of the exchanged planes per step.
 
-Prints ONE JSON line (rank 0) with the driver's contract keys plus `roofline` (dominant kernel
-k_inputs_dense timed with HIP events on the stepper's own stream) and `cpu_baseline` (the oracle --
-a C restatement of the reference's CPU path -- timed on a bounded column sample, rank 0, N = 1).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times exactly --steps steps once and
+prints the headline keys (metric, value, unit, higher_is_better, dtype, ms_per_step).  `--full` adds
+everything else: repetitions of the timed region until they add up to a second, the state checksum,
+`roofline` (dominant kernel k_inputs_dense timed with HIP events on the stepper's own stream), the
+rates with history capture and with a driven spike load, the device's HBM ceilings, per-rank clocks
+and `cpu_baseline` (the oracle -- a C restatement of the reference's CPU path -- timed on a bounded
+column sample, rank 0, N = 1).  `--dump-outputs DIR` writes the state the timed steps leave behind.
 """
 import argparse
 import json
@@ -201,11 +205,29 @@ def cpu_baseline(n, threads, budget_s=15.0):
     return sample_cols * steps / dt, dt, steps, sample_cols, threads, extra
 
 
-def state_checksum(dn, np, dist, rank, world):
-    """sha256 over (current_voltage bits, last_firing_time, is_spiking, per-neuron spike totals) of ALL neurons in global
-    index order -- each rank contributes the neurons it owns.  Post-population sharding does not change any result
-    (the reduction order is defined on the global presynaptic index), so the value must not depend on --gpus."""
-    import hashlib
+def gather_columns(np, dist, rank, world, own, vals, n=None):
+    """rank 0: the [..., n] array whose columns `own` (global postsynaptic indices) each rank holds in `vals`; None elsewhere.
+    With n None every column must be owned by some rank (n = their count)."""
+    mine = (own, vals)
+    parts = [mine]
+    if dist is not None:                       # (also at world size 1 under --force-sharded: the same calls every N makes)
+        parts = [None] * world
+        dist.all_gather_object(parts, mine)
+    if rank != 0:
+        return None
+    total = sum(p[0].size for p in parts)
+    table = np.zeros(vals.shape[:-1] + (total if n is None else n,), vals.dtype)
+    seen = np.zeros(table.shape[-1], bool)
+    for idx, v in parts:
+        table[..., idx] = v
+        seen[idx] = True
+    assert seen.all(), "some neuron is owned by no rank"
+    return table
+
+
+def gather_state(dn, np, dist, rank, world):
+    """rank 0: uint32 [4, n] -- current_voltage bits, last_firing_time, is_spiking, per-neuron spike totals -- of ALL neurons
+    in global index order, each rank contributing the neurons it owns; None elsewhere"""
     own = np.asarray(dn.owned, dtype=np.int64)
     cols = []
     for name, dtype in (("current_voltage", np.float32), ("last_firing_time", np.int32), ("is_spiking", np.uint32)):
@@ -213,21 +235,56 @@ def state_checksum(dn, np, dist, rank, world):
         cols.append(full[own].view(np.uint32))
     counts = np.concatenate([dn.spike_counts(i) for i, (_, _, st) in sorted(dn.lattices.items()) if not st])
     cols.append(counts[own].astype(np.uint32))
-    mine = (own, np.stack(cols))
-    parts = [mine]
-    if dist is not None:                       # (also at world size 1 under --force-sharded: the same calls every N makes)
-        parts = [None] * world
-        dist.all_gather_object(parts, mine)
+    return gather_columns(np, dist, rank, world, own, np.stack(cols))
+
+
+def state_checksum(dn, np, dist, rank, world):
+    """sha256 over gather_state's table.  Post-population sharding does not change any result (the reduction order is
+    defined on the global presynaptic index), so the value must not depend on --gpus."""
+    import hashlib
+    table = gather_state(dn, np, dist, rank, world)
+    return None if table is None else hashlib.sha256(table.tobytes()).hexdigest()
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MAX_NEURONS = 1 << 20          # larger networks: a fixed, seeded sample of this many neurons (24 B each in the dump)
+DUMP_ROWS_BYTES = 16 << 20          # plastic configs: presynaptic rows of the weight matrix (and of the traces), seeded sample
+
+
+def dump_outputs(out_dir, dn, np, dist, rank, world, config):
+    """--dump-outputs: what a caller of the timed path reads back after its last step, as DIR/<name>.npy -- every neuron's
+    voltage, last firing step, spike flag and spike total (f32 / f64, exact), and where the step rewrites the synapses
+    (c4: STDP, c6: R-STDP) a seeded sample of presynaptic rows of the weights (absent edges 0) and of c6's traces.  Every
+    rank takes part in the gathers; rank 0 writes.  Returns the names written (rank 0)."""
+    table = gather_state(dn, np, dist, rank, world)
+    rows = {}
+    if config in ("c4", "c6"):
+        own = np.asarray(dn.owned, dtype=np.int64)
+        k = int(min(32, max(1, DUMP_ROWS_BYTES // (4 * dn.n_neurons)), dn.n_tot))
+        pre = np.sort(np.random.default_rng(7).choice(dn.n_tot, k, replace=False))
+        w = np.empty((k, own.size), np.float32)
+        for j, p in enumerate(pre):
+            wr, cr = dn.get_graph_rows(int(p), 1)
+            w[j] = np.where(cr[0, own] != 0, wr[0, own], np.float32(0))
+        rows["weight_rows_sample"] = gather_columns(np, dist, rank, world, own, w, dn.n_neurons)
+        if config == "c6":
+            t = np.stack([dn.get_trace_rows(int(p), 1)[0, own] for p in pre])
+            rows["trace_rows_sample"] = gather_columns(np, dist, rank, world, own, t, dn.n_neurons)
     if rank != 0:
         return None
-    n = sum(p[0].size for p in parts)
-    table = np.zeros((4, n), np.uint32)
-    seen = np.zeros(n, bool)
-    for idx, vals in parts:
-        table[:, idx] = vals
-        seen[idx] = True
-    assert seen.all(), "some neuron is owned by no rank"
-    return hashlib.sha256(table.tobytes()).hexdigest()
+    n = table.shape[1]
+    pick = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_NEURONS, replace=False)) if n > DUMP_MAX_NEURONS else slice(None)
+    arrays = {"voltage": table[0].view(np.float32)[pick],
+              "last_firing_time": table[1].view(np.int32)[pick].astype(np.float64),
+              "is_spiking": table[2][pick].astype(np.float32),
+              "spike_count": table[3][pick].astype(np.float64)}
+    arrays.update({name: a[:, pick] for name, a in rows.items()})
+    size = sum(a.nbytes for a in arrays.values())
+    assert size <= DUMP_MAX_BYTES, f"--dump-outputs would write {size} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
 
 
 def build_config(args, snn_amd, synthetic, np, rank, world, local_rank):
@@ -323,11 +380,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed repetitions of --steps steps inside this process; the line reports the median")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: repetitions of the timed region (--repeats), the state checksum, "
+                         "spike rate, kernel events and roofline, the rates with history capture and with a driven spike load, the "
+                         "device's HBM ceilings, per-rank clocks, exchange figures and the CPU baseline.  Off: the timed region runs "
+                         "--steps steps once and the line holds the headline keys")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the state they leave (voltages, firing times, spike flags and totals; a "
+                         "sample of the weight rows where the step rewrites them) as DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed repetitions of --steps steps inside this process; the line reports the median (default 1; "
+                         "--full: 5, and more until they add up to a second)")
     ap.add_argument("--rows", type=int, default=ROWS)
     ap.add_argument("--cols", type=int, default=COLS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--spike-fraction", type=float, default=0.0,
                     help="synthetic drive: before every step this fraction of the neurons is raised above threshold "
                          "(device-side generator, snn_set_synthetic_drive), e.g. --config c4 --spike-fraction 0.001 to "
@@ -338,7 +404,7 @@ def main():
                     help="who drives a sharded run: snn_run_sharded (the library calls RCCL itself, default) or "
                          "parallel.ShardedStepper (torch.distributed moves the segments)")
     ap.add_argument("--no-kernel-events", action="store_true",
-                    help="do not bracket k_inputs_dense with HIP events (roofline.achieved is then null)")
+                    help="--full: do not bracket k_inputs_dense with HIP events (roofline.achieved is then null)")
     ap.add_argument("--peer-form", action="store_true",
                     help="--config c5, --gpus N > 1: TRY the peer form of the sparse shard step.  The ranks map each other's receive sets "
                          "after the warm-up (IPC handles through torch.distributed) and step in the peer form -- one launch per step, no "
@@ -463,20 +529,22 @@ def main():
         barrier()
         run(args.warmup)
         extra_steps = 8 + args.warmup
-    spikes_before = own_spike_total()
-    # HIP events around the dominant kernel: inside the timed region for the streaming configs with ms-scale steps (2 event
-    # records per step are noise next to a 2.5 - 13 ms step); for the short-step configs (c1: 4 us, c5: 43 us, c3: 0.19 ms per
-    # step) they would cost 2 - 15 % of the step, so those take them in one extra repetition after the timed ones
-    events_inline = not args.no_kernel_events and args.config not in ("c1", "c3", "c5")
-    events_after = not args.no_kernel_events and not events_inline
+    spikes_before = own_spike_total() if args.full else 0
+    # --full: HIP events around the dominant kernel: inside the timed region for the streaming configs with ms-scale steps (2
+    # event records per step are noise next to a 2.5 - 13 ms step); for the short-step configs (c1: 4 us, c5: 43 us, c3: 0.19 ms
+    # per step) they would cost 2 - 15 % of the step, so those take them in one extra repetition after the timed ones
+    events_inline = args.full and not args.no_kernel_events and args.config not in ("c1", "c3", "c5")
+    events_after = args.full and not args.no_kernel_events and not events_inline
     dn.profile_enable(events_inline)
     dn.profile_reset()
     # the timed region (EXACTLY --steps steps between barrier + synchronize on both sides, max over ranks)
-    # is repeated --repeats times back to back; the line reports the MEDIAN repetition and lists all of them
-    # ... and, for short steps, as many more as it takes for the timed regions to add up to MIN_TIMED_S (the same count on every
-    # rank: decided from the max-over-ranks times)
+    # is repeated --repeats times back to back (once in a plain run); the line reports the MEDIAN repetition
+    # ... and, --full, for short steps, as many more as it takes for the timed regions to add up to MIN_TIMED_S (the same count on
+    # every rank: decided from the max-over-ranks times)
+    repeats = max(1, args.repeats if args.repeats is not None else (5 if args.full else 1))
     runs = []
-    while len(runs) < max(1, args.repeats) or (sum(runs) < MIN_TIMED_S and len(runs) < MAX_REPEATS):
+    state_sha = state_steps = None
+    while len(runs) < repeats or (args.full and sum(runs) < MIN_TIMED_S and len(runs) < MAX_REPEATS):
         barrier()
         t0 = time.perf_counter()
         run(args.steps)
@@ -487,11 +555,12 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             e = float(t.item())
         runs.append(e)
-        if len(runs) == max(1, args.repeats):
+        if args.full and len(runs) == repeats:
             # N = 1 and N = 8 lines can be diffed: a checksum of the network's state right after the --repeats repetitions asked
             # for (the same number of steps for every N, whatever is added below), every rank's own neurons gathered to rank 0
             state_sha, state_steps = state_checksum(dn, np, dist, rank, world), args.warmup + extra_steps + args.steps * len(runs)
     elapsed = sorted(runs)[len(runs) // 2]
+    dumped = dump_outputs(args.dump_outputs, dn, np, dist, rank, world, args.config) if args.dump_outputs else None
     phases = None
     if events_after:
         spikes_timed = own_spike_total()
@@ -505,18 +574,19 @@ def main():
         if args.config == "c1" and not sharded and dn.stat("run_timing_steps"):
             clocks = {k: dn.stat("run_timing_" + k) for k in ("poll", "barrier", "turns", "update")}
             phases = {"steps": dn.stat("run_timing_steps"), "clocks_per_step": {k: v / dn.stat("run_timing_steps") for k, v in clocks.items()}}
-    launches, kern_ms = dn.profile_read()
-    pl_steps, pl_ms = dn.profile_read_plasticity()
-    dn.profile_enable(False)
-    spikes = (spikes_timed if events_after else own_spike_total()) - spikes_before           # of this rank's own neurons
-    if dist is not None:
-        t = torch.tensor([spikes], dtype=torch.float64, device=red)
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        spikes = int(t.item())
-    total_steps = args.steps * len(runs)
+    if args.full:
+        launches, kern_ms = dn.profile_read()
+        pl_steps, pl_ms = dn.profile_read_plasticity()
+        dn.profile_enable(False)
+        spikes = (spikes_timed if events_after else own_spike_total()) - spikes_before           # of this rank's own neurons
+        if dist is not None:
+            t = torch.tensor([spikes], dtype=torch.float64, device=red)
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            spikes = int(t.item())
+        total_steps = args.steps * len(runs)
 
     hist_value = None
-    if not sharded and args.config == "c2":
+    if args.full and not sharded and args.config == "c2":
         # also report the rate with GridVoltageHistory capture on (one extra 4 B store per neuron-step)
         dn.set_history(voltage=True, spikes=True)
         hsteps = min(args.steps, 100)
@@ -528,7 +598,7 @@ def main():
         dn.set_history(voltage=False, spikes=False)
 
     spiking_value = None
-    if not sharded and args.config == "c2" and args.spike_fraction == 0:
+    if args.full and not sharded and args.config == "c2" and args.spike_fraction == 0:
         # the lattice falls silent within the warm-up (gap junctions pull the voltages together): also report the rate with
         # 0.1 % of the population driven above threshold before every step (10 Hz at dt = 0.1 ms), so that the raster ballots,
         # spike totals and last_firing_time stamps are exercised -- AFTER the state checksum, which stays that of the plain run
@@ -549,7 +619,7 @@ def main():
     # rank's own time for --steps steps of the full step, and -- collective form -- of the same loop with a transport that moves
     # nothing (snn_exchange_noop; the state is stale afterwards, which is why this comes after the checksum)
     rank_times = None
-    if sharded and world > 1 and comm is not None:
+    if args.full and sharded and world > 1 and comm is not None:
         barrier()
         t0 = time.perf_counter()
         run(args.steps)
@@ -569,20 +639,33 @@ def main():
                       "exchange_ms_by_rank": [a - b for a, b in parts] if only_ms is not None else None}
 
     ceilings = None
-    if rank == 0 and not sharded and args.config == "c2":
+    if args.full and rank == 0 and not sharded and args.config == "c2":
         dn.synchronize()
         rd, cp = snn_amd.probe_bandwidth(8 << 30, 5, local_rank)     # this device's own HBM ceilings
         ceilings = {"read_only_GBps": rd, "copy_GBps": cp}
 
     # evidence of the transport: ncclCommCount of the communicator the library's loop called RCCL on, and what this rank
     # puts on / takes off the wire per step (the exchange plan's segments, 4 B per word)
-    rccl_ranks = comm.count()[0] if comm is not None else None
+    rccl_ranks = comm.count()[0] if args.full and comm is not None else None
     exchange_bytes = None
-    if sharded:
+    if args.full and sharded:
         plan = dn.exchange_plan()
         exchange_bytes = {"mode": plan["mode"], "sent": 4 * int(plan["send_words"]), "received": 4 * int(plan["recv_words"])}
     if rank == 0:
         value = n * args.steps / elapsed
+        out = {
+            "metric": "neuron-steps/sec", "value": value, "unit": "neuron-steps/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+            "repeats": len(runs), "timed_s": sum(runs),
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": workload, "neurons": n,
+                       "parallelism": f"post-population shards x{world}" if world > 1 else "single GPU"},
+            "full": args.full,
+        }
+        if dumped is not None:
+            out["outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "after_steps": args.warmup + extra_steps + args.steps * len(runs)}
+    if rank == 0 and args.full:
         if not sharded and dn.stat("persistent_run_launches"):
             # all steps of a run call in ONE launch (small electrical-only lattices): `launches` counts its steps
             kernel_name = "k_run_resident<0,true> (many steps per launch; launches = steps)"
@@ -595,11 +678,8 @@ def main():
         bytes_per_launch = dn.input_kernel_bytes()
         avg_ms = kern_ms / max(1, launches)
         achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if launches and avg_ms > 0 else 0.0
-        out = {
-            "metric": "neuron-steps/sec", "value": value, "unit": "neuron-steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "repeats": len(runs), "timed_s": sum(runs), "ms_per_step_runs": [r / args.steps * 1e3 for r in runs[:32]],
+        out.update({
+            "ms_per_step_runs": [r / args.steps * 1e3 for r in runs[:32]],
             "ms_per_step_min": min(runs) / args.steps * 1e3, "ms_per_step_max": max(runs) / args.steps * 1e3,
             "spikes_per_step": spikes / total_steps,
             "state_sha256": state_sha, "state_after_steps": state_steps,
@@ -613,9 +693,6 @@ def main():
                           if emulated else ("RCCL" if sharded else None)),
             "halo_peer_steps": (dn.stat("halo_peer_steps") if sharded else None), "peer_form": peer_note, "rank_times": rank_times,
             "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": workload, "neurons": n,
-                       "parallelism": f"post-population shards x{world}" if world > 1 else "single GPU"},
             "value_with_voltage_and_spike_history": hist_value,
             "value_with_0p1pct_of_the_neurons_spiking_per_step": spiking_value,
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -628,7 +705,7 @@ def main():
                          "kernel_events": ("inside the timed region" if events_inline else
                                            "one extra repetition after the timed ones" if events_after else "off"),
                          "algorithmic_bytes_per_launch": bytes_per_launch},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline and args.config in ("c1", "c2"):
             visible_cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
             v, secs, cpu_steps, sample, threads, extra = cpu_baseline(n, visible_cpus)
@@ -655,9 +732,7 @@ def main():
                                "kernel_events": "one extra repetition after the timed ones",
                                "note": "all steps of a run call in one launch; the matrix stays in registers / LDS, per step "
                                        "only 8 B per neuron travel (L2 / fabric)"}
-        result = json.dumps(out)
-    else:
-        result = None
+    result = json.dumps(out) if rank == 0 else None
 
     dn.close()
     if comm is not None:

@@ -14,7 +14,7 @@ prof() {   # name, bench args...
     local name=$1; shift
     want "$name" || return 0
     rm -rf "$OUT/prof_$name"
-    rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$name" -- python3 bench.py "$@" --no-cpu-baseline \
+    rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$name" -- python3 bench.py --full "$@" --no-cpu-baseline \
         > "$OUT/${name}_bench_under_rocprof.json" 2> "$OUT/${name}_rocprof.err"
     find "$OUT/prof_$name" -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} "$OUT/${name}_kernel_stats.csv"
     grep '^{"metric"' "$OUT/${name}_bench_under_rocprof.json" | tail -1 > "$OUT/${name}_bench_line.json"; mv "$OUT/${name}_bench_line.json" "$OUT/${name}_bench_under_rocprof.json"
@@ -26,7 +26,7 @@ pmc() {    # name, kernel substring, bench args...
     want "$name" || return 0
     for c in FETCH_SIZE WRITE_SIZE; do
         rm -rf "$OUT/pmc_${name}_$c"
-        rocprofv3 --pmc $c --output-format csv -d "$OUT/pmc_${name}_$c" -- python3 bench.py "$@" --no-cpu-baseline --no-kernel-events \
+        rocprofv3 --pmc $c --output-format csv -d "$OUT/pmc_${name}_$c" -- python3 bench.py --full "$@" --no-cpu-baseline --no-kernel-events \
             > /dev/null 2> "$OUT/${name}_pmc_$c.err"
     done
     python3 profiles/summarize_pmc.py "$(find "$OUT/pmc_${name}_FETCH_SIZE" -name '*counter_collection.csv' | head -1)" \
@@ -56,7 +56,7 @@ if want c5; then
 # what ONE rank of G does per step, without its exchange (the library's loop with a transport that moves nothing)
 python3 profiles/measure_c5_rank_step.py 2000 > "$OUT/c5_rank_step.jsonl" 2> /dev/null
 PEER=1 python3 profiles/measure_c5_rank_step.py 2000 > "$OUT/c5_rank_step_peer_form.jsonl" 2> /dev/null
-python3 bench.py --config c5 --no-cpu-baseline > "$OUT/c5_bench_default.json" 2> /dev/null
+python3 bench.py --full --config c5 --no-cpu-baseline > "$OUT/c5_bench_default.json" 2> /dev/null
 rm -rf "$OUT/trace_g8"
 ( cd /tmp && SHARDS=8 rocprofv3 --kernel-trace --output-format csv -d "$OUT/trace_g8" -- python3 "$OLDPWD/profiles/measure_c5_rank_step.py" 1000 > /dev/null 2>&1 )
 python3 profiles/experiments/kernel_gaps.py "$(find "$OUT/trace_g8" -name '*kernel_trace.csv' | head -1)" 400 > "$OUT/c5_rank_step_g8_kernel_trace_summary.json"
@@ -69,14 +69,14 @@ python3 profiles/measure_small_chem.py 3000 2> /dev/null | grep lattice > "$OUT/
 # small plastic lattices: the STDP updates inside the one-launch run against one launch per step + the scatter kernels
 python3 profiles/measure_small_stdp.py 3000 2> /dev/null | grep lattice > "$OUT/small_stdp_lattices.jsonl"
 # the default lines (no profiler): headline, c1 with the latency roofline, c3, c5
-python3 bench.py > "$OUT/bench_default.json" 2> /dev/null
-python3 bench.py --config c1 --no-cpu-baseline > "$OUT/c1_bench_default.json" 2> /dev/null
-python3 bench.py --config c3 --no-cpu-baseline > "$OUT/c3_bench_default.json" 2> /dev/null
+python3 bench.py --full > "$OUT/bench_default.json" 2> /dev/null
+python3 bench.py --full --config c1 --no-cpu-baseline > "$OUT/c1_bench_default.json" 2> /dev/null
+python3 bench.py --full --config c3 --no-cpu-baseline > "$OUT/c3_bench_default.json" 2> /dev/null
 # round 5: C3 in four fresh processes, with and without the closing input pass; C4 with 1 % of the neurons spiking; small plastic lattices
-for i in 1 2 3 4; do python3 bench.py --config c3 --no-cpu-baseline > "$OUT/c3_fresh_process_$i.json" 2> /dev/null; done
+for i in 1 2 3 4; do python3 bench.py --full --config c3 --no-cpu-baseline > "$OUT/c3_fresh_process_$i.json" 2> /dev/null; done
 # (the two-kernel step is the default -- the four lines above; this arm is the closing pass, option "dense_close" 1)
-for i in 1 2; do SNN_AMD_DENSE_CLOSE=1 python3 bench.py --config c3 --no-cpu-baseline > "$OUT/c3_closing_pass_process_$i.json" 2> /dev/null; done
-python3 bench.py --config c4 --spike-fraction 0.01 --steps 50 --warmup 100 --repeats 2 --no-cpu-baseline > "$OUT/c4_spiking_1pct_bench.json" 2> /dev/null
+for i in 1 2; do SNN_AMD_DENSE_CLOSE=1 python3 bench.py --full --config c3 --no-cpu-baseline > "$OUT/c3_closing_pass_process_$i.json" 2> /dev/null; done
+python3 bench.py --full --config c4 --spike-fraction 0.01 --steps 50 --warmup 100 --repeats 2 --no-cpu-baseline > "$OUT/c4_spiking_1pct_bench.json" 2> /dev/null
 python3 profiles/measure_small_plastic.py 3000 > "$OUT/small_plastic_lattices.jsonl" 2> /dev/null
 fi
 ls "$OUT"

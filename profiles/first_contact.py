@@ -6,7 +6,7 @@ script runs, in order, what has to be known first and leaves ONE table behind.
     python3 profiles/first_contact.py --emulate --gpus-list 1,2 --rows 48       # rehearsal on a one-GPU box (nothing measured)
 
  1. tests/test_gpu_multi_device.py (2 / 4 / 8 real ranks over RCCL against the oracle; skipped below 2 visible GPUs).
- 2. bench.py --gpus N for N in --gpus-list:
+ 2. bench.py --full --gpus N for N in --gpus-list:
       c2 strong                 the headline lattice, post-population shards, ncclAllGather of voltages + spike bits
       c5 strong, collective     4 x 512 x 512 + Poisson cells, shards by lattice, grouped ncclSend / ncclRecv of the halo
       c5 strong, peer form      the same with --peer-form (tried; falls back by agreement)
@@ -30,10 +30,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def series(args):
-    common = ["--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu-baseline"]
+    common = ["--full", "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu-baseline"]
     # bench.py --peer-form runs warm-up, an 8-step trial and a second warm-up before the timed region: the collective series
     # of c5 gets the same number of steps as its warm-up, so that the two forms can be held against each other checksum by checksum
-    common5 = ["--steps", str(args.steps), "--warmup", str(2 * args.warmup + 8), "--no-cpu-baseline"]
+    common5 = ["--full", "--steps", str(args.steps), "--warmup", str(2 * args.warmup + 8), "--no-cpu-baseline"]
     small = (["--rows", str(args.rows), "--cols", str(args.rows)] if args.rows else [])
     out = [("c2 strong", ["--config", "c2"] + small + common, "strong"),
            ("c5 strong collective", ["--config", "c5"] + (["--rows", str(args.rows)] if args.rows else []) + common5, "strong"),

@@ -17,7 +17,7 @@ W, K = 6, 10
 
 
 def bench(*flags, gpus=2, warmup=W):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--config", "c5", "--rows", "48", "--steps", str(K), "--warmup", str(warmup),
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(gpus), "--config", "c5", "--rows", "48", "--steps", str(K), "--warmup", str(warmup),
            "--repeats", "2", "--no-cpu-baseline", "--no-kernel-events", *flags]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])

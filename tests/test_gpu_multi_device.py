@@ -84,7 +84,7 @@ def test_bench_state_checksum_does_not_depend_on_the_gpu_count(config, extra):
         pytest.skip(f"needs at least 2 GPUs, {visible_gpus()} visible")
     sums = {}
     for world in worlds:
-        args = [os.path.join(ROOT, "bench.py"), "--config", config, "--gpus", str(world), "--steps", "30", "--warmup", "5",
+        args = [os.path.join(ROOT, "bench.py"), "--full", "--config", config, "--gpus", str(world), "--steps", "30", "--warmup", "5",
                 "--repeats", "2", "--no-cpu-baseline", "--spike-fraction", "0.002"] + extra
         r = launch(world, args)
         assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -104,7 +104,7 @@ def test_bench_state_checksum_of_the_sharded_path_at_world_size_one(config, extr
         pytest.skip("no GPU")
     sums = {}
     for forced in (False, True):
-        args = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--steps", "20", "--warmup", "3", "--repeats", "2",
+        args = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", config, "--steps", "20", "--warmup", "3", "--repeats", "2",
                 "--no-cpu-baseline", "--spike-fraction", "0.002"] + extra + (["--force-sharded"] if forced else [])
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()))
         r = subprocess.run(args, cwd=ROOT, env=env, capture_output=True, text=True, timeout=800)

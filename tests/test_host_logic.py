@@ -83,6 +83,80 @@ def test_bench_single_gpu_stays_in_process(tmp_path):
     assert launched is None and proc.returncode != 0 and "must not import torch" in proc.stderr
 
 
+class _FakeHandle:
+    """the few DeviceNetwork reads bench.dump_outputs makes, from host arrays (one neuron lattice + one spike-train lattice)"""
+
+    def __init__(self, n, seed=3):
+        rng = np.random.default_rng(seed)
+        self.n_neurons = self.n_tot = n
+        self.lattices = {0: (1, n, False), 1: (1, 5, True)}
+        self.owned = np.arange(n)
+        self.attrs = {"current_voltage": rng.uniform(-70, 30, n).astype(np.float32),
+                      "last_firing_time": rng.integers(-1, 500, n).astype(np.int32),
+                      "is_spiking": rng.integers(0, 2, n).astype(np.uint32)}
+        self.counts = rng.integers(0, 9, n).astype(np.uint32)
+        self.w = rng.uniform(0.5, 1.5, (n, n)).astype(np.float32)
+        self.c = (rng.uniform(size=(n, n)) < 0.8).astype(np.uint32)
+        self.trace = rng.uniform(size=(n, n)).astype(np.float32)
+
+    def get_attr(self, id, name, dtype=np.float32):
+        assert id == 0
+        return self.attrs[name].astype(dtype)
+
+    def spike_counts(self, id):
+        assert id == 0
+        return self.counts.copy()
+
+    def get_graph_rows(self, pre, count):
+        return self.w[pre:pre + count].copy(), self.c[pre:pre + count].copy()
+
+    def get_trace_rows(self, pre, count):
+        return self.trace[pre:pre + count].copy()
+
+
+def test_bench_dump_outputs_writes_the_state_as_float_arrays(tmp_path):
+    """--dump-outputs: voltages (f32), firing times and spike totals (f64), spike flags (f32), exactly; for a plastic config a
+    seeded sample of weight rows (absent edges 0) and, c6, of traces; the same handle gives the same files"""
+    import bench
+    dn = _FakeHandle(300)
+    names = bench.dump_outputs(str(tmp_path / "a"), dn, np, None, 0, 1, "c6")
+    assert names == ["is_spiking", "last_firing_time", "spike_count", "trace_rows_sample", "voltage", "weight_rows_sample"]
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in names}
+    assert got["voltage"].dtype == np.float32 and np.array_equal(got["voltage"], dn.attrs["current_voltage"])
+    assert got["last_firing_time"].dtype == np.float64 and np.array_equal(got["last_firing_time"], dn.attrs["last_firing_time"])
+    assert got["is_spiking"].dtype == np.float32 and np.array_equal(got["is_spiking"], dn.attrs["is_spiking"])
+    assert got["spike_count"].dtype == np.float64 and np.array_equal(got["spike_count"], dn.counts)
+    w, t = got["weight_rows_sample"], got["trace_rows_sample"]
+    assert w.shape == t.shape == (32, 300) and w.dtype == t.dtype == np.float32
+    rows = [next(p for p in range(300) if np.array_equal(t[j], dn.trace[p])) for j in range(32)]
+    assert rows == sorted(set(rows))
+    assert np.array_equal(w, np.where(dn.c[rows] != 0, dn.w[rows], np.float32(0)))
+    assert bench.dump_outputs(str(tmp_path / "b"), dn, np, None, 0, 1, "c6") == names
+    assert all(np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy")) for k in names)
+    assert bench.dump_outputs(str(tmp_path / "c"), dn, np, None, 0, 1, "c2") == ["is_spiking", "last_firing_time", "spike_count", "voltage"]
+
+
+def test_bench_dump_outputs_samples_a_large_network(tmp_path, monkeypatch):
+    """more neurons than DUMP_MAX_NEURONS: a fixed, seeded sample of them, in ascending index order"""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_NEURONS", 100)
+    dn = _FakeHandle(1000)
+    bench.dump_outputs(str(tmp_path / "a"), dn, np, None, 0, 1, "c2")
+    bench.dump_outputs(str(tmp_path / "b"), dn, np, None, 0, 1, "c2")
+    v = np.load(tmp_path / "a" / "voltage.npy")
+    assert v.shape == (100,) and np.array_equal(v, np.load(tmp_path / "b" / "voltage.npy"))
+    idx = [int(np.flatnonzero(dn.attrs["current_voltage"] == x)[0]) for x in v]
+    assert idx == sorted(set(idx))
+    assert np.array_equal(np.load(tmp_path / "a" / "spike_count.npy"), dn.counts[idx])
+
+
+def test_bench_options_parse_before_torch(tmp_path):
+    """--full and --dump-outputs are options of the plain command line, read before torch is imported"""
+    proc, launched = _bench_under_stub(tmp_path, ["--help"])
+    assert proc.returncode == 0 and launched is None, proc.stderr
+    assert "--full" in proc.stdout and "--dump-outputs" in proc.stdout
+
+
 def test_c5_structure_on_rectangular_lattices():
     """the weak-scaling form of bench.py --config c5: four (rows x cols) lattices; checked against a plain double loop"""
     from snn_amd import synthetic
@@ -114,7 +188,7 @@ def _first_contact(tmp_path, behaviour):
         "ap = argparse.ArgumentParser()\n"
         "for f in ('--gpus', '--steps', '--warmup', '--rows', '--cols'): ap.add_argument(f, type=int, default=1)\n"
         "ap.add_argument('--config'); ap.add_argument('--scaling', default='strong')\n"
-        "for f in ('--peer-form', '--no-cpu-baseline', '--emulate-ranks-on-one-gpu'): ap.add_argument(f, action='store_true')\n"
+        "for f in ('--full', '--peer-form', '--no-cpu-baseline', '--emulate-ranks-on-one-gpu'): ap.add_argument(f, action='store_true')\n"
         "a = ap.parse_args()\n"
         "extra = 8 + a.warmup if a.peer_form else 0\n"
         "steps = a.warmup + extra + 5 * a.steps\n"

@@ -1,7 +1,5 @@
 """The neuron-description front end (spiking-neural-networks_amd/modelgen.py) on the CPU: it reads the reference's own
 DSL file, refuses what it does not implement, and emits the expected HIP for the pieces that carry the arithmetic."""
-import os
-
 import numpy as np
 import pytest
 
@@ -32,9 +30,6 @@ def test_parses_the_reference_fixture():
     src = modelgen.hip_source(m)
     assert "const float d_v = (((v - x[0]) + i_in)) * dt;" in src and "v += d_v;" in src
     assert "const bool spiking = (v >= x[2]);" in src and "v = x[1];" in src
-    path = "/root/reference/build_test/nb_macro/tests/lif.nb"
-    if os.path.exists(path):                       # this container only: the committed text equals the reference's file
-        assert modelgen.parse(open(path).read()).variables == m.variables
 
 
 def test_mandatory_overrides_precedence_and_order_of_application():
