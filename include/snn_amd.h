@@ -176,7 +176,8 @@ int snn_fill_graph_synthetic(snn_network_t *net, uint64_t seed, float lo, float 
  * BASELINE configs[4]).  snn_network_use_csr must precede finalize; a handle is dense or CSR for life.
  * row_ptr[n_local + 1] (row_ptr[0] == 0, row_ptr[n_local] == nnz), pre_index[nnz] = interleaved
  * presynaptic index, STRICTLY ascending inside each row, weights[nnz].  Stored edges are Some(w),
- * everything else is None.  Same arithmetic as the dense form, bit for bit. */
+ * everything else is None.  Same arithmetic as the dense form, bit for bit.  All or nothing: a call that fails
+ * leaves the previous graph in place (a reward-modulated handle may be left with the new graph but without its traces). */
 int snn_network_use_csr(snn_network_t *net, int enable);
 int snn_set_graph_csr(snn_network_t *net, const uint64_t *row_ptr, const uint32_t *pre_index,
                       const float *weights, uint64_t nnz);

@@ -78,50 +78,13 @@ int snn_network_destroy(snn_network_t *net) ABI_TRY
     if (!net) return SNN_OK;
     (void)hipSetDevice(net->device);
     if (net->stream) (void)hipStreamSynchronize(net->stream);
-    for (void *p : net->allocs) (void)hipFree(p);
-    for (void *p : {(void *)net->csr_ptr, (void *)net->csr_pre, (void *)net->csr_post, (void *)net->csr_t_ptr,
-                    (void *)net->csr_t_edge, (void *)net->csr_w, (void *)net->csr_row_len, (void *)net->csr_edge_slot,
-                    (void *)net->csr_plan, (void *)net->csr_img_hdr, (void *)net->csr_plan_win, (void *)net->csr_img_rec,
-                    (void *)net->csr_img_hdr_direct, (void *)net->csr_plan_win_direct, (void *)net->csr_img_rec_direct})
-        if (p) (void)hipFree(p);
-    if (net->vhist) (void)hipFree(net->vhist);
-    if (net->st_vhist) (void)hipFree(net->st_vhist);
-    if (net->raster) (void)hipFree(net->raster);
-    if (net->preset_times_dev) (void)hipFree(net->preset_times_dev);
-    if (net->trace) (void)hipFree(net->trace);
-    if (net->pending) (void)hipFree(net->pending);
-    if (net->edge_counter) (void)hipFree(net->edge_counter);
-    if (net->cross_bad) (void)hipFree(net->cross_bad);
-    if (net->conn_kind_dev) (void)hipFree(net->conn_kind_dev);
-    if (net->run_failed) (void)hipHostFree(net->run_failed);
-    if (net->copy_stage) (void)hipHostFree(net->copy_stage);
-    if (net->st_clock_pinned) (void)hipHostFree(net->st_clock_pinned);
-    if (net->verify_report) (void)hipFree(net->verify_report);
-    if (net->verify_big) (void)hipFree(net->verify_big);
-    if (net->verify_third) (void)hipFree(net->verify_third);
-    for (float *b : net->whist) if (b) (void)hipFree(b);
-    if (net->summ_avg) (void)hipFree(net->summ_avg);
-    if (net->summ_eeg) (void)hipFree(net->summ_eeg);
     for (auto &e : net->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (auto &e : net->ev_pool_pl) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    if (net->cell_list_dev) (void)hipFree(net->cell_list_dev);
-    for (void *p : {(void *)net->halo_send_buf2, (void *)net->halo_recv_buf2, (void *)net->csr_plan_direct, (void *)net->halo_word_dev})
-        if (p) (void)hipFree(p);
-    for (void *p : {(void *)net->halo_send_buf, (void *)net->halo_recv_buf, (void *)net->halo_send_idx, (void *)net->halo_recv_idx,
-                    (void *)net->seg_count_dev[0], (void *)net->seg_count_dev[1], (void *)net->seg_first_dev[0],
-                    (void *)net->seg_first_dev[1], (void *)net->seg_offset_dev[0], (void *)net->seg_offset_dev[1],
-                    (void *)net->seg_loff_dev[0], (void *)net->seg_loff_dev[1], (void *)net->csr_border_dev,
-                    (void *)net->csr_interior_dev, (void *)net->pack_ptr_dev, (void *)net->pack_segoff_dev,
-                    (void *)net->pack_count_dev, (void *)net->pack_index_dev})
-        if (p) (void)hipFree(p);
-    (void)p2p_release(net, /*final=*/true);
-    if (net->p2p_failed) (void)hipHostFree(net->p2p_failed);
-    if (net->agree_words_dev) (void)hipFree(net->agree_words_dev);
     if (net->comm_stream) { (void)hipStreamSynchronize(net->comm_stream); (void)hipStreamDestroy(net->comm_stream); }
     if (net->ev_packed) (void)hipEventDestroy(net->ev_packed);
     if (net->ev_exchanged) (void)hipEventDestroy(net->ev_exchanged);
     if (net->own_stream) (void)hipStreamDestroy(net->own_stream);
-    delete net;
+    delete net;                        // the owners free every buffer (IPC mappings are the caller's: snn_p2p_ipc_close)
     return SNN_OK;
 }
 ABI_CATCH
@@ -227,9 +190,6 @@ static int finalize_impl(snn_network_t *net, int kind, uint32_t post_begin, uint
         HIP_TRY(copy_sync(net, net->own_block_dev, blocks.data(), blocks.size() * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
         HIP_TRY(copy_sync(net, net->own_mask_dev, masks.data(), masks.size() * 8, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
         HIP_TRY(copy_sync(net, net->local_row_dev, net->local_row_host.data(), (size_t)net->n_pad * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        net->allocs.push_back(net->own_block_dev);
-        net->allocs.push_back(net->own_mask_dev);
-        net->allocs.push_back(net->local_row_dev);
         net->rowmap = RowMap{0, net->own_block_dev, net->own_mask_dev, net->local_row_dev};
     }
     net->ld = std::max<uint32_t>(64, round_up(net->n_loc, 64));
@@ -393,6 +353,9 @@ ABI_CATCH
 
 namespace { int ensure_traces(snn_network *net); int ensure_pending(snn_network *net); }
 
+// All or nothing: a failed call leaves the previous graph in place, intact -- except that the traces / dw / counters of a handle
+// with modulation or connection kinds are sized by the new graph and allocated after the commit: if THAT fails, the handle holds
+// the new graph without them.  Device memory peaks at old graph + new graph while the call runs.
 static int set_graph_csr_impl(snn_network_t *net, const uint64_t *row_ptr, const uint32_t *pre_index, const float *weights,
                               uint64_t nnz)
 {
@@ -453,66 +416,81 @@ static int set_graph_csr_impl(snn_network_t *net, const uint64_t *row_ptr, const
     }
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
     TRY(end_run(net));
-    for (void **p : {(void **)&net->csr_ptr, (void **)&net->csr_pre, (void **)&net->csr_post, (void **)&net->csr_t_ptr,
-                     (void **)&net->csr_t_edge, (void **)&net->csr_w, (void **)&net->csr_row_len,
-                     (void **)&net->csr_edge_slot, (void **)&net->csr_plan, (void **)&net->csr_img_hdr, (void **)&net->csr_plan_win,
-                     (void **)&net->csr_img_rec}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    auto up = [&](void **dst, const void *src, size_t bytes) -> int {
+    // everything of the new graph goes into locals first (device arrays, gather plan, step image, halo lists, cell list); the
+    // commit below only moves and swaps
+    dev_ptr<uint32_t> slice_ptr_d, pre_d, row_len_d, edge_slot_d, post_d, t_ptr_d, t_edge_d, plan_d, img_hdr_d, plan_win_d;
+    dev_ptr<float> w_d;
+    dev_ptr<uint4> img_rec_d;
+    auto up = [&](auto *dst, const void *src, size_t bytes) -> int {
         HIP_TRY(snn_malloc(dst, std::max<size_t>(bytes, 256)), SNN_ERR_BUFFER_CREATE);
         if (bytes) HIP_TRY(copy_sync(net, *dst, src, bytes, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
         return SNN_OK;
     };
-    TRY(up((void **)&net->csr_ptr, slice_ptr.data(), slice_ptr.size() * 4));
-    TRY(up((void **)&net->csr_pre, sell_pre.data(), entries * 4));
-    TRY(up((void **)&net->csr_w, sell_w.data(), entries * 4));
-    TRY(up((void **)&net->csr_row_len, row_len.data(), row_len.size() * 4));
-    TRY(up((void **)&net->csr_edge_slot, edge_slot.data(), nnz * 4));
-    TRY(up((void **)&net->csr_post, post.data(), nnz * 4));
-    TRY(up((void **)&net->csr_t_ptr, t_ptr.data(), t_ptr.size() * 4));
-    TRY(up((void **)&net->csr_t_edge, t_edge.data(), nnz * 4));
-    HIP_TRY(snn_malloc(&net->csr_plan, std::max<size_t>(entries * 4, 256)), SNN_ERR_BUFFER_CREATE);
+    TRY(up(&slice_ptr_d, slice_ptr.data(), slice_ptr.size() * 4));
+    TRY(up(&pre_d, sell_pre.data(), entries * 4));
+    TRY(up(&w_d, sell_w.data(), entries * 4));
+    TRY(up(&row_len_d, row_len.data(), row_len.size() * 4));
+    TRY(up(&edge_slot_d, edge_slot.data(), nnz * 4));
+    TRY(up(&post_d, post.data(), nnz * 4));
+    TRY(up(&t_ptr_d, t_ptr.data(), t_ptr.size() * 4));
+    TRY(up(&t_edge_d, t_edge.data(), nnz * 4));
+    HIP_TRY(snn_malloc(&plan_d, std::max<size_t>(entries * 4, 256)), SNN_ERR_BUFFER_CREATE);
+    uint64_t img_records = 0, img_staged_slices = 0;
     {
         // the step image's host-built half: slice headers with the window pieces, and the plan words that go with them
         hvec<uint32_t> img_hdr, plan_win;
-        build_step_image_plan(net, slice_ptr, sell_pre, n_slices, img_hdr, plan_win, net->img_records, net->img_staged_slices);
-        TRY(up((void **)&net->csr_img_hdr, img_hdr.data(), img_hdr.size() * 4));
-        TRY(up((void **)&net->csr_plan_win, plan_win.data(), plan_win.size() * 4));
-        HIP_TRY(snn_malloc(&net->csr_img_rec, (size_t)net->img_records * 16 + 4096), SNN_ERR_BUFFER_CREATE);    // (+ a wavefront's load of slack)
-        net->img_stale = true;
+        build_step_image_plan(net, slice_ptr, sell_pre, n_slices, img_hdr, plan_win, img_records, img_staged_slices);
+        TRY(up(&img_hdr_d, img_hdr.data(), img_hdr.size() * 4));
+        TRY(up(&plan_win_d, plan_win.data(), plan_win.size() * 4));
+        HIP_TRY(snn_malloc(&img_rec_d, (size_t)img_records * 16 + 4096), SNN_ERR_BUFFER_CREATE);    // (+ a wavefront's load of slack)
     }
-    if (net->trace) { (void)hipFree(net->trace); net->trace = nullptr; }      // traces belong to the replaced edges
-    for (float **m : {&net->pending, &net->edge_counter})                     // ... and so do dw and the counters of its connections
-        if (*m) { (void)hipFree(*m); *m = nullptr; }
-    net->cross_checked = false;
-    net->nnz = nnz;
-    net->sell_entries = entries;
     if (n_slices) {
-        hipLaunchKernelGGL(k_csr_plan, dim3((n_slices * 64 + 255) / 256), dim3(256), 0, net->stream, csr_graph(net),
-                           net->csr_plan, (const uint32_t *)nullptr, net->nn, PLAN_CODE);
+        SellGraph g = csr_graph(net);                 // (the handle's geometry, the new arrays)
+        g.slice_ptr = slice_ptr_d; g.pre = pre_d; g.w = w_d; g.row_len = row_len_d;
+        g.edge_slot = edge_slot_d; g.edge_post = post_d; g.t_ptr = t_ptr_d; g.t_edge = t_edge_d; g.plan = plan_d;
+        hipLaunchKernelGGL(k_csr_plan, dim3((n_slices * 64 + 255) / 256), dim3(256), 0, net->stream, g,
+                           plan_d, (const uint32_t *)nullptr, net->nn, PLAN_CODE);
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
     }
-    net->edge_slot_host.swap(edge_slot);
-    if (net->sharded && net->n_shards > 1) { net->sell_pre_host.swap(sell_pre); net->slice_ptr_host.swap(slice_ptr); }
-    else { net->sell_pre_host.clear(); net->slice_ptr_host.clear(); }
-    net->img_stale_direct = true;
-    net->counts_dirty = true;
-    halo_needs_from_rows(net, pre_index, nnz);      // the new rows decide what is read from the other shards
-    if (net->sharded && net->n_shards > 1 && net->nc) {
-        // ... and which spike-train cells this rank reads at all
+    // the new rows decide what is read from the other shards, and which spike-train cells this rank reads at all
+    hvec<hvec<uint32_t>> halo_need(net->n_shards), halo_send(net->n_shards);
+    halo_needs_from_rows(net, pre_index, nnz, halo_need);
+    const bool list_cells = net->sharded && net->n_shards > 1 && net->nc;
+    hvec<uint32_t> cells;
+    dev_ptr<uint32_t> cells_d;
+    if (list_cells) {
         hvec<uint8_t> seen(net->nc, 0);
         for (uint64_t e = 0; e < nnz; ++e)
             if (pre_index[e] >= net->nn) seen[pre_index[e] - net->nn] = 1;
-        net->cell_list_host.clear();
         for (uint32_t s = 0; s < net->nc; ++s)
-            if (seen[s]) net->cell_list_host.push_back(s);
-        TRY(upload_table(net, &net->cell_list_dev, net->cell_list_host));
+            if (seen[s]) cells.push_back(s);
+        TRY(upload_table(net, &cells_d, cells));
+    }
+    // ---- the commit ----
+    net->csr_ptr = std::move(slice_ptr_d); net->csr_pre = std::move(pre_d); net->csr_w = std::move(w_d);
+    net->csr_row_len = std::move(row_len_d); net->csr_edge_slot = std::move(edge_slot_d); net->csr_post = std::move(post_d);
+    net->csr_t_ptr = std::move(t_ptr_d); net->csr_t_edge = std::move(t_edge_d); net->csr_plan = std::move(plan_d);
+    net->csr_img_hdr = std::move(img_hdr_d); net->csr_plan_win = std::move(plan_win_d); net->csr_img_rec = std::move(img_rec_d);
+    net->img_records = img_records; net->img_staged_slices = img_staged_slices;
+    net->img_stale = net->img_stale_direct = true;
+    net->trace = nullptr;                                        // traces belong to the replaced edges
+    net->pending = nullptr; net->edge_counter = nullptr;         // ... and so do dw and the counters of its connections
+    net->cross_checked = false;
+    net->nnz = nnz;
+    net->sell_entries = entries;
+    net->edge_slot_host.swap(edge_slot);
+    if (net->sharded && net->n_shards > 1) { net->sell_pre_host.swap(sell_pre); net->slice_ptr_host.swap(slice_ptr); }
+    else { net->sell_pre_host.clear(); net->slice_ptr_host.clear(); }
+    net->counts_dirty = true;
+    net->halo_need.swap(halo_need); net->halo_send.swap(halo_send);
+    net->halo_committed = false; net->x_dirty = true;
+    if (list_cells) {
+        net->cell_list_host.swap(cells);
+        net->cell_list_dev = std::move(cells_d);
         net->n_cells_listed = (uint32_t)net->cell_list_host.size();
         net->view_dirty = true;
     }
-    // a reward-modulated handle keeps modulating: zeroed traces for the new edges (the old ones went with their edges)
+    // a reward-modulated handle keeps modulating: zeroed traces for the new edges, sized by the committed graph (see above)
     if (net->any_modulation || net->any_conn_kind) TRY(ensure_traces(net));
     if (net->any_conn_kind) TRY(ensure_pending(net));
     return SNN_OK;
@@ -632,7 +610,7 @@ int ensure_traces(snn_network *net)
 {
     if (net->trace) return SNN_OK;
     const size_t n = std::max<size_t>(trace_elems(net), 64);
-    HIP_TRY(alloc_streamed(reinterpret_cast<void **>(&net->trace), n * 4), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(alloc_streamed(&net->trace, n * 4), SNN_ERR_BUFFER_CREATE);
     HIP_TRY(hipMemsetAsync(net->trace, 0, n * 4, net->stream), SNN_ERR_BUFFER_WRITE);
     // The trace matrix of a dense handle is rewritten every step (k_inputs_rstdp): like the synapse matrix its HBM placement
     // decides a few per cent of the pass (choose_matrix_placement) -- up to three more candidates, each held until the
@@ -640,25 +618,25 @@ int ensure_traces(snn_network *net)
     if (!net->csr && n * 4 >= ((size_t)1 << 30)) {
         float best = 0.0f;
         int rc = time_rw_pass(net, net->trace, n / 4, &best);
-        hvec<void *> losers;
+        hvec<dev_ptr<float>> losers;                 // (freed after the search, see choose_matrix_placement)
         for (int cand = 0; cand < 3 && rc == SNN_OK; ++cand) {
             size_t free_b = 0, total_b = 0;
-            void *b = nullptr;
+            dev_ptr<float> b;
             if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < n * 4 + (n >> 0) || alloc_streamed(&b, n * 4) != hipSuccess) break;
             float ms = 0.0f;
-            if (hipMemsetAsync(b, 0, n * 4, net->stream) != hipSuccess) { losers.push_back(b); break; }
-            rc = time_rw_pass(net, static_cast<float *>(b), n / 4, &ms);
+            if (hipMemsetAsync(b, 0, n * 4, net->stream) != hipSuccess) { losers.push_back(std::move(b)); break; }
+            rc = time_rw_pass(net, b, n / 4, &ms);
             if (getenv("SNN_DEBUG_PLACEMENT"))
-                fprintf(stderr, "[snn] trace placement (%zu vectors): held %p %.3f ms, candidate %p %.3f ms\n", n / 4, (void *)net->trace, best, b, ms);
+                fprintf(stderr, "[snn] trace placement (%zu vectors): held %p %.3f ms, candidate %p %.3f ms\n", n / 4, (void *)net->trace.get(), best,
+                        (void *)b.get(), ms);
             if (rc == SNN_OK && ms < best * 0.99f) {
-                losers.push_back(net->trace);
-                net->trace = static_cast<float *>(b);
+                losers.push_back(std::move(net->trace));
+                net->trace = std::move(b);
                 best = ms;
             } else {
-                losers.push_back(b);
+                losers.push_back(std::move(b));
             }
         }
-        for (void *p : losers) (void)hipFree(p);
         if (rc) return rc;
     }
     return SNN_OK;
@@ -780,7 +758,7 @@ static int trace_rows_io(snn_network_t *net, uint32_t pre_begin, uint32_t pre_co
     // through a row-major staging block of <= 64 MiB and <= 32768 rows per hop (the matrix is in quad-row order)
     float *host = traces + net->q0;
     const uint32_t hop = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(pre_count, 32768), ((size_t)64 << 20) / ((size_t)net->n_loc * 4)));
-    float *stage = nullptr;
+    dev_ptr<float> stage;
     HIP_TRY(snn_malloc(&stage, (size_t)hop * net->n_loc * 4), SNN_ERR_BUFFER_CREATE);
     int rc = SNN_OK;
     for (uint32_t r = 0; r < pre_count && rc == SNN_OK; r += hop) {
@@ -798,7 +776,6 @@ static int trace_rows_io(snn_network_t *net, uint32_t pre_begin, uint32_t pre_co
                             hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SNN_ERR_BUFFER_READ, "trace download failed");
         }
     }
-    (void)hipFree(stage);
     return rc;
 }
 int snn_set_trace_rows(snn_network_t *net, uint32_t pre_begin, uint32_t pre_count, const float *traces) ABI_TRY
@@ -991,14 +968,13 @@ int snn_set_firing_times(snn_network_t *net, uint32_t id, const uint32_t *cell_p
         flat.insert(flat.end(), net->preset_host[s].begin(), net->preset_host[s].end());
     }
     for (size_t s = net->nc; s <= net->c_pad; ++s) ptr[s] = (uint32_t)flat.size();
-    float *nt = nullptr;
+    dev_ptr<float> nt;
     HIP_TRY(snn_malloc(&nt, std::max<size_t>(256, flat.size() * 4)), SNN_ERR_BUFFER_CREATE);
     if (!flat.empty()) HIP_TRY(copy_sync(net, nt, flat.data(), flat.size() * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
     HIP_TRY(copy_sync(net, const_cast<uint32_t *>(net->ca.preset_ptr), ptr.data(), ptr.size() * 4, hipMemcpyHostToDevice),
             SNN_ERR_BUFFER_WRITE);
-    if (net->preset_times_dev) (void)hipFree(net->preset_times_dev);
-    net->preset_times_dev = nt;
     net->ca.preset_times = nt;
+    net->preset_times_dev = std::move(nt);
     return SNN_OK;
 }
 ABI_CATCH
@@ -1207,10 +1183,8 @@ int snn_debug_checkpoint(snn_network_t *net, int restore) ABI_TRY
     if (restore) net->img_stale = net->img_stale_direct = true;          // the sparse weights come back: the step image's records are rebuilt
     auto &cp = net->checkpoint;
     hvec<std::pair<void *, size_t>> arrays;
-    for (const auto &kv : net->alloc_bytes)
-        if (kv.first != (void *)net->snap_buf && kv.first != (void *)net->snap_table && kv.first != (void *)net->verify_buf &&
-            kv.first != (void *)net->run_granules && kv.first != (void *)net->run_partials && kv.first != (void *)net->run_timing)
-            arrays.emplace_back(kv.first, kv.second);
+    for (const auto &r : net->registry)
+        if (!r.scratch) arrays.emplace_back(r.mem.get(), r.bytes);
     if (net->csr_w) arrays.emplace_back(net->csr_w, (size_t)net->sell_entries * 4);
     if (net->trace) arrays.emplace_back(net->trace, std::max<size_t>(trace_elems(net), 64) * 4);
     for (void *m : {(void *)net->pending, (void *)net->edge_counter})
@@ -1407,14 +1381,10 @@ int snn_run(snn_network_t *net, uint64_t iterations) ABI_TRY
     TRY(flush_stdp(net));
     TRY(run_snapshot(net, /*restore=*/false));                    // (builds the table; its own copy of S(t) is not used here)
     if (!net->verify_buf || net->verify_words < net->snap_words) {
-        if (net->verify_buf) {
-            (void)hipFree(net->verify_buf);
-            net->alloc_bytes.erase(net->verify_buf);
-            net->allocs.erase(std::remove(net->allocs.begin(), net->allocs.end(), (void *)net->verify_buf), net->allocs.end());
-            net->verify_buf = nullptr;
-        }
+        dev_replace(net, net->verify_buf);
+        net->verify_buf = nullptr;
         net->verify_words = net->snap_words + net->snap_words / 4 + 1024;
-        TRY(dev_alloc_t(net, &net->verify_buf, 2 * net->verify_words));
+        TRY(dev_alloc_t(net, &net->verify_buf, 2 * net->verify_words, /*scratch=*/true));
         TRY(run_snapshot(net, /*restore=*/false));                // the handle has allocated: the table is laid out anew
     }
     if (!net->verify_report) HIP_TRY(snn_malloc(&net->verify_report, 256), SNN_ERR_BUFFER_CREATE);
@@ -1435,7 +1405,6 @@ int snn_run(snn_network_t *net, uint64_t iterations) ABI_TRY
     size_t big = 0;
     for (const auto &m : matrices) big += m.second;
     if (big > net->verify_big_bytes) {
-        if (net->verify_big) (void)hipFree(net->verify_big);
         net->verify_big = nullptr; net->verify_big_bytes = 0;
         HIP_TRY(snn_malloc(&net->verify_big, 2 * big), SNN_ERR_BUFFER_CREATE);
         net->verify_big_bytes = big;
@@ -1534,7 +1503,6 @@ int snn_run(snn_network_t *net, uint64_t iterations) ABI_TRY
             // outcome.
             if (matrices.empty()) {
                 if (net->verify_third_words < net->verify_words) {
-                    if (net->verify_third) (void)hipFree(net->verify_third);
                     net->verify_third = nullptr; net->verify_third_words = 0;
                     HIP_TRY(snn_malloc(&net->verify_third, net->verify_words * 4), SNN_ERR_BUFFER_CREATE);
                     net->verify_third_words = net->verify_words;
@@ -1855,18 +1823,14 @@ int snn_comm_exchange_halo_lists(snn_network_t *net, void *nccl_comm) ABI_TRY
     // (1) counts: row `me` of a G x G matrix, all-gathered; (2) the lists themselves, grouped send / recv
     hvec<uint32_t> counts((size_t)G * G, 0);
     for (uint32_t p = 0; p < G; ++p) counts[(size_t)me * G + p] = (uint32_t)net->halo_need[p].size();
-    uint32_t *d_counts = nullptr;
+    dev_ptr<uint32_t> d_counts, d_need, d_send;
     HIP_TRY(snn_malloc(&d_counts, counts.size() * 4), SNN_ERR_BUFFER_CREATE);
-    int rc = SNN_OK;
-    uint32_t *d_need = nullptr, *d_send = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_counts); if (d_need) (void)hipFree(d_need); if (d_send) (void)hipFree(d_send); };
-#define HALO_STEP(expr) do { rc = (expr); if (rc) { cleanup(); return rc; } } while (0)
     auto hip_ok = [&](hipError_t e, int code, const char *what) { return e == hipSuccess ? SNN_OK : fail(code, std::string(what) + ": " + hipGetErrorString(e)); };
     auto nccl_ok = [&](ncclResult_t r, const char *what) { return r == ncclSuccess ? SNN_OK : fail(SNN_ERR_QUEUE, std::string(what) + ": " + R->GetErrorString(r)); };
-    HALO_STEP(hip_ok(copy_sync(net, d_counts, counts.data(), counts.size() * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE, "counts upload"));
-    HALO_STEP(nccl_ok(R->AllGather(d_counts + (size_t)me * G, d_counts, G, ncclUint32, comm, net->stream), "ncclAllGather(counts)"));
-    HALO_STEP(hip_ok(hipStreamSynchronize(net->stream), SNN_ERR_WAIT, "counts wait"));
-    HALO_STEP(hip_ok(copy_sync(net, counts.data(), d_counts, counts.size() * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ, "counts download"));
+    TRY(hip_ok(copy_sync(net, d_counts, counts.data(), counts.size() * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE, "counts upload"));
+    TRY(nccl_ok(R->AllGather(d_counts + (size_t)me * G, d_counts, G, ncclUint32, comm, net->stream), "ncclAllGather(counts)"));
+    TRY(hip_ok(hipStreamSynchronize(net->stream), SNN_ERR_WAIT, "counts wait"));
+    TRY(hip_ok(copy_sync(net, counts.data(), d_counts, counts.size() * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ, "counts download"));
     hvec<uint64_t> need_off(G + 1, 0), send_off(G + 1, 0);
     for (uint32_t p = 0; p < G; ++p) {
         need_off[p + 1] = need_off[p] + counts[(size_t)me * G + p];        // what I ask of p
@@ -1874,11 +1838,11 @@ int snn_comm_exchange_halo_lists(snn_network_t *net, void *nccl_comm) ABI_TRY
     }
     hvec<uint32_t> need_flat(need_off[G]), send_flat(send_off[G]);
     for (uint32_t p = 0; p < G; ++p) std::copy(net->halo_need[p].begin(), net->halo_need[p].end(), need_flat.begin() + need_off[p]);
-    HALO_STEP(hip_ok(snn_malloc(&d_need, std::max<size_t>(need_flat.size() * 4, 256)), SNN_ERR_BUFFER_CREATE, "hipMalloc"));
-    HALO_STEP(hip_ok(snn_malloc(&d_send, std::max<size_t>(send_flat.size() * 4, 256)), SNN_ERR_BUFFER_CREATE, "hipMalloc"));
+    TRY(hip_ok(snn_malloc(&d_need, std::max<size_t>(need_flat.size() * 4, 256)), SNN_ERR_BUFFER_CREATE, "hipMalloc"));
+    TRY(hip_ok(snn_malloc(&d_send, std::max<size_t>(send_flat.size() * 4, 256)), SNN_ERR_BUFFER_CREATE, "hipMalloc"));
     if (!need_flat.empty())
-        HALO_STEP(hip_ok(copy_sync(net, d_need, need_flat.data(), need_flat.size() * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE, "lists upload"));
-    HALO_STEP(nccl_ok(R->GroupStart(), "ncclGroupStart"));
+        TRY(hip_ok(copy_sync(net, d_need, need_flat.data(), need_flat.size() * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE, "lists upload"));
+    TRY(nccl_ok(R->GroupStart(), "ncclGroupStart"));
     {
         // a failure inside the group still closes it (a dangling group would swallow every later RCCL call of this thread)
         int first = SNN_OK;
@@ -1890,14 +1854,12 @@ int snn_comm_exchange_halo_lists(snn_network_t *net, void *nccl_comm) ABI_TRY
                 first = nccl_ok(R->Recv(d_send + send_off[p], send_off[p + 1] - send_off[p], ncclUint32, (int)p, comm, net->stream), "ncclRecv(list)");
         }
         const ncclResult_t closed = R->GroupEnd();
-        HALO_STEP(first);
-        HALO_STEP(nccl_ok(closed, "ncclGroupEnd"));
+        TRY(first);
+        TRY(nccl_ok(closed, "ncclGroupEnd"));
     }
-    HALO_STEP(hip_ok(hipStreamSynchronize(net->stream), SNN_ERR_WAIT, "lists wait"));
+    TRY(hip_ok(hipStreamSynchronize(net->stream), SNN_ERR_WAIT, "lists wait"));
     if (!send_flat.empty())
-        HALO_STEP(hip_ok(copy_sync(net, send_flat.data(), d_send, send_flat.size() * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ, "lists download"));
-#undef HALO_STEP
-    cleanup();
+        TRY(hip_ok(copy_sync(net, send_flat.data(), d_send, send_flat.size() * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ, "lists download"));
     for (uint32_t p = 0; p < G; ++p) {
         if (p == me) continue;
         TRY(snn_halo_set_sends(net, p, send_flat.data() + send_off[p], (uint32_t)(send_off[p + 1] - send_off[p])));
@@ -1915,9 +1877,9 @@ int snn_p2p_local(snn_network_t *net, uint64_t *recv0, uint64_t *recv1, uint64_t
     TRY(ensure_exchange_plan(net));
     if (!net->peer_capable || !net->p2p_recv[0])
         return fail(SNN_ERR_BAD_STATE, "the peer form needs a committed halo plan in which something travels");
-    *recv0 = reinterpret_cast<uint64_t>(net->p2p_recv[0]);
-    *recv1 = reinterpret_cast<uint64_t>(net->p2p_recv[1]);
-    *flags = reinterpret_cast<uint64_t>(net->p2p_flags);
+    *recv0 = reinterpret_cast<uint64_t>(net->p2p_recv[0].get());
+    *recv1 = reinterpret_cast<uint64_t>(net->p2p_recv[1].get());
+    *flags = reinterpret_cast<uint64_t>(net->p2p_flags.get());
     for (uint32_t p = 0; p < net->n_shards; ++p) {
         if (recv_offsets) recv_offsets[p] = net->x_recv_off[p];
         if (recv_counts) recv_counts[p] = net->halo_need[p].size();
@@ -2073,7 +2035,7 @@ static int agree_on_exchange(Rccl *R, snn_network *net, ncclComm_t comm, void *n
     // rank that freed these words here waited for a neighbour's first peer-form launch, which was polling for this rank's: a
     // give-up after the spin limit, 3 of 16 runs of the emulated-rank tests in round 6.  And a run path has no business
     // synchronising the device.)
-    if (net->agree_words_dev && net->agree_words_cap < G) { (void)hipFree(net->agree_words_dev); net->agree_words_dev = nullptr; }
+    if (net->agree_words_cap < G) net->agree_words_dev = nullptr;
     if (!net->agree_words_dev) {
         HIP_TRY(snn_malloc(&net->agree_words_dev, std::max<size_t>((size_t)G * 4, 256)), SNN_ERR_BUFFER_CREATE);
         net->agree_words_cap = G;
@@ -2458,14 +2420,11 @@ int snn_probe_bandwidth(int device, uint64_t bytes, int repeats, double *read_gb
     if (bytes < (1u << 20) || repeats <= 0) return fail(SNN_ERR_BAD_ARG, "need >= 1 MiB and >= 1 repeat");
     HIP_TRY(hipSetDevice(device), SNN_ERR_GET_DEVICE);
     const size_t n4 = bytes / 16;
-    void *a = nullptr, *b = nullptr;
-    float *sink = nullptr;
+    dev_ptr<probe_v4f> a, b;
+    dev_ptr<float> sink;
     HIP_TRY(snn_malloc(&a, n4 * 16), SNN_ERR_BUFFER_CREATE);
-    if (snn_malloc(&b, n4 * 16) != hipSuccess || snn_malloc(&sink, 256) != hipSuccess) {
-        (void)hipFree(a);
-        if (b) (void)hipFree(b);
+    if (snn_malloc(&b, n4 * 16) != hipSuccess || snn_malloc(&sink, 256) != hipSuccess)
         return fail(SNN_ERR_BUFFER_CREATE, "probe allocation failed");
-    }
     int rc = SNN_OK;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (hipMemset(a, 0, n4 * 16) != hipSuccess || hipMemset(b, 0, n4 * 16) != hipSuccess ||
@@ -2492,7 +2451,6 @@ int snn_probe_bandwidth(int device, uint64_t bytes, int repeats, double *read_gb
     if (rc == SNN_OK) timed(true, copy_gbps);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(a); (void)hipFree(b); (void)hipFree(sink);
     return rc;
 }
 ABI_CATCH
@@ -2503,9 +2461,9 @@ int snn_probe_math(int device, int which, const float *in, float *out, size_t co
     if (which < 0 || which > 2) return fail(SNN_ERR_BAD_ARG, "unknown function selector");
     HIP_TRY(hipSetDevice(device), SNN_ERR_GET_DEVICE);
     if (count == 0) return SNN_OK;
-    float *di = nullptr, *dout = nullptr;
+    dev_ptr<float> di, dout;
     HIP_TRY(snn_malloc(&di, count * 4), SNN_ERR_BUFFER_CREATE);
-    if (snn_malloc(&dout, count * 4) != hipSuccess) { (void)hipFree(di); return fail(SNN_ERR_BUFFER_CREATE, "hipMalloc failed"); }
+    if (snn_malloc(&dout, count * 4) != hipSuccess) return fail(SNN_ERR_BUFFER_CREATE, "hipMalloc failed");
     int rc = SNN_OK;
     if (hipMemcpy(di, in, count * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(SNN_ERR_BUFFER_WRITE, "upload failed");
     if (rc == SNN_OK) {
@@ -2513,8 +2471,6 @@ int snn_probe_math(int device, int which, const float *in, float *out, size_t co
         if (hipDeviceSynchronize() != hipSuccess) rc = fail(SNN_ERR_WAIT, "probe kernel failed");
     }
     if (rc == SNN_OK && hipMemcpy(out, dout, count * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SNN_ERR_BUFFER_READ, "download failed");
-    (void)hipFree(di);
-    (void)hipFree(dout);
     return rc;
 }
 ABI_CATCH
@@ -2525,13 +2481,12 @@ int snn_probe_math_bits(int device, int which, uint32_t first, uint32_t stride, 
     if (which < 0 || which > 6) return fail(SNN_ERR_BAD_ARG, "unknown function selector");
     HIP_TRY(hipSetDevice(device), SNN_ERR_GET_DEVICE);
     if (count == 0) return SNN_OK;
-    float *dout = nullptr;
+    dev_ptr<float> dout;
     HIP_TRY(snn_malloc(&dout, count * 4), SNN_ERR_BUFFER_CREATE);
     int rc = SNN_OK;
     hipLaunchKernelGGL(k_probe_math_bits, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, which, first, stride, y, dout, count);
     if (hipDeviceSynchronize() != hipSuccess) rc = fail(SNN_ERR_WAIT, "probe kernel failed");
     if (rc == SNN_OK && hipMemcpy(out, dout, count * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SNN_ERR_BUFFER_READ, "download failed");
-    (void)hipFree(dout);
     return rc;
 }
 ABI_CATCH

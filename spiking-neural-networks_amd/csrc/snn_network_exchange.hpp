@@ -14,13 +14,15 @@ namespace {
 
 inline uint64_t segment_words(uint32_t planes, uint64_t count) { return (uint64_t)planes * count + (count + 31) / 32; }
 
-template <typename T>
-int upload_table(snn_network *net, T **dev, const hvec<T> &host)
+// a device copy of `host` in place of *dev (which keeps the old table if that fails)
+template <typename T, typename U>
+int upload_table(snn_network *net, dev_ptr<T> *dev, const hvec<U> &host)
 {
-    if (*dev) { (void)hipFree(*dev); *dev = nullptr; }
-    HIP_TRY(snn_malloc(dev, std::max<size_t>(host.size() * sizeof(T), 256)), SNN_ERR_BUFFER_CREATE);
+    dev_ptr<T> fresh;
+    HIP_TRY(snn_malloc(&fresh, std::max<size_t>(host.size() * sizeof(U), 256)), SNN_ERR_BUFFER_CREATE);
     if (!host.empty())
-        HIP_TRY(copy_sync(net, *dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        HIP_TRY(copy_sync(net, fresh, host.data(), host.size() * sizeof(U), hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+    *dev = std::move(fresh);
     return SNN_OK;
 }
 
@@ -55,24 +57,17 @@ void synthesize_full_lists(snn_network *net)
 }
 
 // the peer form's buffers and connection belong to ONE plan: a rebuilt plan starts unconnected
-int p2p_release(snn_network *net, bool final = false)
+int p2p_release(snn_network *net)
 {
     // What PEERS may still address -- the two receive sets and the done counters, by committed tables or IPC mappings of the
     // old plan -- is not freed here but kept until this handle is destroyed: a neighbour that
     // announces "my previous launch is over" at the start of its next run stores into these words (include/snn_amd.h: peers
     // reconnect after a plan rebuild; until they have, their stores land in memory that is still this handle's).
-    for (void *b : {(void *)net->p2p_recv[0], (void *)net->p2p_recv[1], (void *)net->p2p_flags})
-        if (b) net->p2p_retired.push_back(b);
-    if (final) {
-        for (void *b : net->p2p_retired) (void)hipFree(b);
-        net->p2p_retired.clear();
-    }
-    for (void *b : {(void *)net->p2p_done_blocks, (void *)net->p2p_dst_dev[0], (void *)net->p2p_dst_dev[1], (void *)net->p2p_peer_dev,
-                    (void *)net->p2p_signal_dev})
-        if (b) (void)hipFree(b);
-    net->p2p_recv[0] = net->p2p_recv[1] = nullptr;
-    net->p2p_flags = nullptr; net->p2p_done_blocks = nullptr;
-    net->p2p_dst_dev[0] = net->p2p_dst_dev[1] = nullptr; net->p2p_peer_dev = nullptr; net->p2p_signal_dev = nullptr;
+    for (auto *b : {&net->p2p_recv[0], &net->p2p_recv[1]})
+        if (*b) net->p2p_retired.emplace_back(std::move(*b));
+    if (net->p2p_flags) net->p2p_retired.emplace_back(std::move(net->p2p_flags));
+    net->p2p_done_blocks = nullptr;
+    net->p2p_dst_dev[0] = nullptr; net->p2p_dst_dev[1] = nullptr; net->p2p_peer_dev = nullptr; net->p2p_signal_dev = nullptr;
     net->p2p_n_signal = 0; net->p2p_recv_words = 0;
     net->p2p_peers.clear();
     net->p2p_connected = false;
@@ -175,21 +170,21 @@ int ensure_exchange_plan(snn_network *net)
         TRY(upload_table(net, &net->pack_count_dev, pack_count));
         TRY(upload_table(net, &net->pack_index_dev, pack_index));
         net->send_bits_clean = true;                 // the send buffer is (re)created zeroed below
-        for (uint32_t **b : {&net->halo_send_buf, &net->halo_recv_buf, &net->halo_send_buf2, &net->halo_recv_buf2,
-                             &net->csr_plan_direct, &net->halo_word_dev})
-            if (*b) { (void)hipFree(*b); *b = nullptr; }
+        for (dev_ptr<uint32_t> *b : {&net->halo_send_buf, &net->halo_recv_buf, &net->halo_send_buf2, &net->halo_recv_buf2,
+                                     &net->csr_plan_direct, &net->halo_word_dev})
+            *b = nullptr;
         // the direct form (see snn_network_state.hpp): voltage is the only plane, so a halo neuron's value is ONE word
         net->direct_capable = net->csr && net->csr_pre && net->electrical && !net->chemical && P == 1 &&
                               (uint64_t)net->nn + net->nc + ro < PLAN_CODE && net->n_loc;
         // the PEER form carries every plane of the plan: one granule per neuron and plane (P adjacent granules per halo neuron
         // fit the words of its segment: P * count + ceil(count / 32) >= P * count)
         net->peer_capable = net->csr && net->csr_pre && P >= 1 && (uint64_t)net->nn + net->nc + ro < PLAN_CODE && net->n_loc;
-        for (uint32_t **b : {&net->halo_send_buf, net->direct_capable ? &net->halo_send_buf2 : nullptr}) {
+        for (dev_ptr<uint32_t> *b : {&net->halo_send_buf, net->direct_capable ? &net->halo_send_buf2 : nullptr}) {
             if (!b) continue;
             HIP_TRY(snn_malloc(b, std::max<uint64_t>(so * 4, 256)), SNN_ERR_BUFFER_CREATE);
             HIP_TRY(memset_sync(net, *b, 0, std::max<uint64_t>(so * 4, 256)), SNN_ERR_BUFFER_WRITE);
         }
-        for (uint32_t **b : {&net->halo_recv_buf, net->direct_capable ? &net->halo_recv_buf2 : nullptr}) {
+        for (dev_ptr<uint32_t> *b : {&net->halo_recv_buf, net->direct_capable ? &net->halo_recv_buf2 : nullptr}) {
             if (!b) continue;
             HIP_TRY(snn_malloc(b, std::max<uint64_t>(ro * 4, 256)), SNN_ERR_BUFFER_CREATE);
             HIP_TRY(memset_sync(net, *b, 0, std::max<uint64_t>(ro * 4, 256)), SNN_ERR_BUFFER_WRITE);
@@ -200,17 +195,17 @@ int ensure_exchange_plan(snn_network *net)
             // kernels of this one read it), zeroed (tag 0 is never expected: epochs start at 1)
             net->p2p_recv_words = ro;
             for (int i = 0; i < 2; ++i) {
-                HIP_TRY(ext_malloc(reinterpret_cast<void **>(&net->p2p_recv[i]), std::max<uint64_t>(ro * 8, 256), hipDeviceMallocFinegrained),
+                HIP_TRY(ext_malloc(&net->p2p_recv[i], std::max<uint64_t>(ro * 8, 256), hipDeviceMallocFinegrained),
                         SNN_ERR_BUFFER_CREATE);
                 HIP_TRY(memset_sync(net, net->p2p_recv[i], 0, std::max<uint64_t>(ro * 8, 256)), SNN_ERR_BUFFER_WRITE);
             }
-            HIP_TRY(ext_malloc(reinterpret_cast<void **>(&net->p2p_flags), std::max<size_t>((size_t)G * 4, 256), hipDeviceMallocFinegrained),
+            HIP_TRY(ext_malloc(&net->p2p_flags, std::max<size_t>((size_t)G * 4, 256), hipDeviceMallocFinegrained),
                     SNN_ERR_BUFFER_CREATE);
             HIP_TRY(memset_sync(net, net->p2p_flags, 0, std::max<size_t>((size_t)G * 4, 256)), SNN_ERR_BUFFER_WRITE);
             HIP_TRY(snn_malloc(&net->p2p_done_blocks, 256), SNN_ERR_BUFFER_CREATE);
             HIP_TRY(memset_sync(net, net->p2p_done_blocks, 0, 256), SNN_ERR_BUFFER_WRITE);
             if (!net->p2p_failed) {
-                HIP_TRY(host_malloc(reinterpret_cast<void **>(&net->p2p_failed), 8, hipHostMallocMapped), SNN_ERR_BUFFER_CREATE);
+                HIP_TRY(host_malloc(&net->p2p_failed, 8, hipHostMallocMapped), SNN_ERR_BUFFER_CREATE);
                 net->p2p_failed[0] = 0u;
             }
             net->p2p_peers.assign(G, snn_network::P2pPeer{});
@@ -231,10 +226,7 @@ int ensure_exchange_plan(snn_network *net)
             HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
             HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
             // the step image of direct runs (voltage the only plane on the wire: a halo neuron is ONE word of the receive buffer)
-            for (void **q : {(void **)&net->csr_img_hdr_direct, (void **)&net->csr_plan_win_direct, (void **)&net->csr_img_rec_direct}) {
-                if (*q) (void)hipFree(*q);
-                *q = nullptr;
-            }
+            net->csr_img_hdr_direct = nullptr; net->csr_plan_win_direct = nullptr; net->csr_img_rec_direct = nullptr;
             if (net->direct_capable && P == 1 && !net->sell_pre_host.empty()) {
                 hvec<uint32_t> img_hdr, plan_win;
                 uint64_t records = 0;
@@ -271,7 +263,7 @@ WireArgs wire_args(snn_network *net, int which, int set)
                  : net->wire;
     a.seg_count = net->seg_count_dev[which]; a.seg_offset = net->seg_offset_dev[which];
     a.seg_first = net->seg_first_dev[which]; a.seg_list_offset = net->seg_loff_dev[which];
-    a.list = halo ? (which == 0 ? net->halo_send_idx : net->halo_recv_idx) : nullptr;
+    a.list = halo ? (which == 0 ? net->halo_send_idx.get() : net->halo_recv_idx.get()) : nullptr;
     a.skip = (!halo && which == 1) ? net->shard_index : 0xFFFFFFFFu;
     a.last_firing_time = net->na.last_firing_time;
     a.clock = net->clock;
@@ -342,10 +334,9 @@ void halo_reset(snn_network *net)
     net->x_dirty = true;
 }
 
-// per peer: the distinct neurons of that peer among the presynaptic indices of the local rows (ascending)
-void halo_needs_from_rows(snn_network *net, const uint32_t *pre_index, uint64_t nnz)
+// per peer: the distinct neurons of that peer among the presynaptic indices of the local rows (ascending), into need[peer]
+void halo_needs_from_rows(const snn_network *net, const uint32_t *pre_index, uint64_t nnz, hvec<hvec<uint32_t>> &need)
 {
-    halo_reset(net);
     if (!net->sharded || net->n_shards < 2) return;
     hvec<uint8_t> seen(net->nn, 0);
     for (uint64_t e = 0; e < nnz; ++e) {
@@ -353,7 +344,7 @@ void halo_needs_from_rows(snn_network *net, const uint32_t *pre_index, uint64_t 
         if (p < net->nn && !owns(net, p)) seen[p] = 1;
     }
     for (uint32_t p = 0; p < net->nn; ++p)
-        if (seen[p]) net->halo_need[owner_of(net, p)].push_back(p);
+        if (seen[p]) need[owner_of(net, p)].push_back(p);
 }
 
 // ---- RCCL, resolved at first use ---------------------------------------------------------------------------------
@@ -610,13 +601,13 @@ int p2p_build_tables(snn_network *net)
         if (!net->p2p_peers[p].set) return fail(SNN_ERR_BAD_STATE, "peer form: shard " + std::to_string(p) + " is read by this shard but is not connected");
         signal.push_back(net->p2p_peers[p].flags + 4ull * me);
     }
-    for (int k = 0; k < 2; ++k) TRY(upload_table(net, reinterpret_cast<unsigned long long **>(&net->p2p_dst_dev[k]), dst[k]));
+    for (int k = 0; k < 2; ++k) TRY(upload_table(net, &net->p2p_dst_dev[k], dst[k]));
     TRY(upload_table(net, &net->p2p_peer_dev, peer));
-    TRY(upload_table(net, reinterpret_cast<unsigned long long **>(&net->p2p_signal_dev), signal));
+    TRY(upload_table(net, &net->p2p_signal_dev, signal));
     net->p2p_n_signal = (uint32_t)signal.size();
     net->p2p_connected = true;
     net->x_agreed = false;                         // whether a run takes the peer form is part of what the ranks agree on
-    // Receive sets of earlier plans stay allocated until the handle is destroyed (p2p_release(final)): THIS handle's commit says
+    // Receive sets of earlier plans stay allocated until the handle is destroyed (p2p_retired): THIS handle's commit says
     // nothing about its peers -- one that has not run its own connect / commit yet still holds tables or IPC mappings into them
     // and would store its next granules or done counters into freed, possibly reallocated memory.  A plan rebuild is rare and a
     // receive set small (8 B per halo neuron), so nothing is gained by freeing earlier.

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -46,7 +47,7 @@ int fail(int code, const std::string &msg)
 // EVERY exported definition in snn_network.hip is a function-try-block -- `int snn_x(...) ABI_TRY { ... } ABI_CATCH` -- whose
 // handler turns whatever arrives into a status code and a message (tests/test_abi.py checks the translation unit for it):
 // std::bad_alloc / std::length_error (a host-side table sized by the caller's numbers) -> SNN_ERR_BUFFER_CREATE, anything else ->
-// SNN_ERR_BAD_STATE.  The handle stays destroyable: device allocations are on record in net->allocs the moment they exist.
+// SNN_ERR_BAD_STATE.  The handle stays destroyable: every device allocation has its owner (dev_ptr, below) the moment it exists.
 int abi_exception(const char *entry) noexcept
 {
     int code = SNN_ERR_BAD_STATE;
@@ -121,15 +122,36 @@ struct HostAlloc {
     template <typename U> bool operator!=(const HostAlloc<U> &) const { return false; }
 };
 template <typename T> using hvec = std::vector<T, HostAlloc<T>>;
-inline hipError_t host_malloc(void **out, size_t bytes, unsigned flags)
+
+// ---- owners: every device / page-locked buffer has ONE (a member of the handle, an entry of its registry -- dev_alloc -- or a
+// local of the call that stages through it), which frees it when reset, replaced or destroyed.  A deleter does not select the
+// device: whatever frees runs after its entry point's hipSetDevice(net->device).  Owners read as T * (kernel arguments, views);
+// a raw pointer cannot be assigned into one.
+struct DevFree { void operator()(void *p) const noexcept { (void)hipFree(p); } };
+struct PinnedFree { void operator()(void *p) const noexcept { (void)hipHostFree(p); } };
+template <typename T, typename Free>
+struct Owned : std::unique_ptr<T, Free> {
+    using std::unique_ptr<T, Free>::unique_ptr;
+    operator T *() const noexcept { return this->get(); }
+};
+template <typename T> using dev_ptr = Owned<T, DevFree>;
+template <typename T> using pinned_ptr = Owned<T, PinnedFree>;
+
+template <typename T>
+inline hipError_t host_malloc(pinned_ptr<T> *out, size_t bytes, unsigned flags)
 {
-    if (alloc_fault_now()) { *out = nullptr; return hipErrorOutOfMemory; }
-    return hipHostMalloc(out, bytes, flags);
+    void *p = nullptr;
+    const hipError_t e = alloc_fault_now() ? hipErrorOutOfMemory : hipHostMalloc(&p, bytes, flags);
+    out->reset(static_cast<T *>(p));
+    return e;
 }
-inline hipError_t ext_malloc(void **out, size_t bytes, unsigned flags)
+template <typename T>
+inline hipError_t ext_malloc(dev_ptr<T> *out, size_t bytes, unsigned flags)
 {
-    if (alloc_fault_now()) { *out = nullptr; return hipErrorOutOfMemory; }
-    return hipExtMallocWithFlags(out, bytes, flags);
+    void *p = nullptr;
+    const hipError_t e = alloc_fault_now() ? hipErrorOutOfMemory : hipExtMallocWithFlags(&p, bytes, flags);
+    out->reset(static_cast<T *>(p));
+    return e;
 }
 
 #define HIP_TRY(expr, code)                                                                      \
@@ -190,16 +212,16 @@ struct snn_network {
     hvec<uint32_t> rm_on_host;
     float *rm_dev = nullptr;
     uint32_t *rm_on_dev = nullptr;
-    float *trace = nullptr;                // dense: [n_tot][ld]; CSR: [sell_entries]
+    dev_ptr<float> trace;                  // dense: [n_tot][ld]; CSR: [sell_entries]
     // connections of a reward-modulated NETWORK that end in a modulated lattice (snn_set_connection_kind, k_reward_cross):
     // conn_kind [n_lattices + n_st_lattices][n_lattices], TraceRSTDP::dw per edge (`pending`, allocated on first use, layout of W),
     // TraceRSTDP::counter per post lattice
     hvec<uint8_t> conn_kind_host;
-    uint8_t *conn_kind_dev = nullptr;
+    dev_ptr<uint8_t> conn_kind_dev;
     bool any_conn_kind = false;
-    float *pending = nullptr;
-    float *edge_counter = nullptr;
-    uint32_t *cross_bad = nullptr;
+    dev_ptr<float> pending;
+    dev_ptr<float> edge_counter;
+    dev_ptr<uint32_t> cross_bad;
     bool cross_checked = false;           // the connection kinds lie where the reference defines their updates (check_reward_cross)
     // Dense handles defer the weight update of step t to the input pass of step t+1 (k_inputs_rstdp: one pass over
     // W and the traces instead of two); any host access to weights / traces / timing flushes it first.
@@ -222,8 +244,8 @@ struct snn_network {
     uint32_t n_owned = 0;
     hvec<uint32_t> owned_local_host;                     // k-th owned neuron (ascending) -> local row
     hvec<uint32_t> local_row_host;                       // [nn] global neuron -> local row or 0xFFFFFFFF
-    uint32_t *own_block_dev = nullptr, *local_row_dev = nullptr;
-    unsigned long long *own_mask_dev = nullptr;
+    dev_ptr<uint32_t> own_block_dev, local_row_dev;
+    dev_ptr<unsigned long long> own_mask_dev;
     RowMap rowmap{};
     // ---- exchange plan (snn_kernels_exchange.hpp), rebuilt by ensure_exchange_plan when x_dirty ----
     bool x_dirty = true;
@@ -242,18 +264,18 @@ struct snn_network {
     // that peer reads (send); buffers and segment tables sized by the plan
     hvec<hvec<uint32_t>> halo_need, halo_send;
     bool halo_committed = false;
-    uint32_t *halo_send_buf = nullptr, *halo_recv_buf = nullptr, *halo_send_idx = nullptr, *halo_recv_idx = nullptr;
+    dev_ptr<uint32_t> halo_send_buf, halo_recv_buf, halo_send_idx, halo_recv_idx;
     hvec<uint64_t> x_send_off, x_send_words, x_recv_off, x_recv_words;     // per peer, in words
     // device segment tables of the pack / unpack launches: {count, offset, first, list offset} per segment
-    uint32_t *seg_count_dev[2] = {nullptr, nullptr}, *seg_first_dev[2] = {nullptr, nullptr};
-    uint64_t *seg_offset_dev[2] = {nullptr, nullptr}, *seg_loff_dev[2] = {nullptr, nullptr};
+    dev_ptr<uint32_t> seg_count_dev[2], seg_first_dev[2];
+    dev_ptr<uint64_t> seg_offset_dev[2], seg_loff_dev[2];
     uint32_t seg_n[2] = {0, 0}, seg_max[2] = {0, 0};
     // one-launch sparse step on shard handles (halo mode, k_step_csr + k_step_close): the 64-row slices that hold a
     // neuron some peer reads (border) and the others (interior); per local row the outgoing-segment positions of its
     // neuron (PackTable); totals of the close launch's unpack / clear jobs
-    uint32_t *csr_border_dev = nullptr, *csr_interior_dev = nullptr;
+    dev_ptr<uint32_t> csr_border_dev, csr_interior_dev;
     uint32_t n_border = 0, n_interior = 0;
-    uint32_t *pack_ptr_dev = nullptr, *pack_segoff_dev = nullptr, *pack_count_dev = nullptr, *pack_index_dev = nullptr;
+    dev_ptr<uint32_t> pack_ptr_dev, pack_segoff_dev, pack_count_dev, pack_index_dev;
     uint32_t recv_total = 0, send_bitmap_words = 0;
     bool send_bits_clean = true;          // every outgoing spike bitmap is zero (what the in-kernel pack ORs into)
     bool update_packed = false;           // this step's own slot of the all-gather buffer was written by k_update
@@ -268,8 +290,8 @@ struct snn_network {
     // t % 2, the exchange fills receive set t % 2, the rows of step t + 1 read it while the exchange of step t + 1 fills the
     // other one.  The mirror copy + last_firing_time stamps of a step's arrivals ride behind the NEXT step's rows
     // (stamp_pending), the last one at the end of the run.
-    uint32_t *halo_send_buf2 = nullptr, *halo_recv_buf2 = nullptr;
-    uint32_t *csr_plan_direct = nullptr, *halo_word_dev = nullptr;
+    dev_ptr<uint32_t> halo_send_buf2, halo_recv_buf2;
+    dev_ptr<uint32_t> csr_plan_direct, halo_word_dev;
     bool direct_capable = false;          // the plan has the direct form (sparse, halo mode, voltage the only plane)
     bool peer_capable = false;            // the plan has the PEER form (sparse, halo mode, any planes)
     uint32_t peer_delay = 0;              // option "halo_peer_delay": injected latencies, in s_sleep(127) units (tests)
@@ -282,21 +304,21 @@ struct snn_network {
     // PEER form of such a run (snn_network_exchange.hpp): the border rows store {value, tag | spike} granules straight into the
     // peers' receive sets, the rows of the next step read them when their tag says so, and a done counter per peer says when a
     // set may be overwritten -- no collective, ONE launch per step.  Needs the peers' addresses (snn_p2p_connect / _commit).
-    unsigned long long *p2p_recv[2] = {nullptr, nullptr};     // [recv words] granules each, fine-grained
-    uint32_t *p2p_flags = nullptr;                            // [n_shards] done counters, written by the peers (fine-grained)
-    uint32_t *p2p_done_blocks = nullptr;
-    uint32_t *p2p_failed = nullptr;                           // host-mapped word: a poll gave up
-    uint32_t *agree_words_dev = nullptr;                      // agree_on_exchange's one word per rank (kept: no hipFree in a run path)
+    dev_ptr<unsigned long long> p2p_recv[2];                  // [recv words] granules each, fine-grained
+    dev_ptr<uint32_t> p2p_flags;                              // [n_shards] done counters, written by the peers (fine-grained)
+    dev_ptr<uint32_t> p2p_done_blocks;
+    pinned_ptr<uint32_t> p2p_failed;                          // host-mapped word: a poll gave up
+    dev_ptr<uint32_t> agree_words_dev;                        // agree_on_exchange's one word per rank (kept: no hipFree in a run path)
     uint32_t agree_words_cap = 0;
     uint64_t p2p_recv_words = 0;
     struct P2pPeer { uint64_t recv[2] = {0, 0}, flags = 0, recv_offset = 0; bool set = false; };
     hvec<P2pPeer> p2p_peers;                           // per shard: where this handle's values go on that peer
-    unsigned long long **p2p_dst_dev[2] = {nullptr, nullptr}; // per pack entry: the peer's granule, per set
-    uint32_t *p2p_peer_dev = nullptr;                         // per pack entry: the peer
-    uint32_t **p2p_signal_dev = nullptr;                      // the neighbours' flags[this shard]
+    dev_ptr<unsigned long long *> p2p_dst_dev[2];             // per pack entry: the peer's granule, per set
+    dev_ptr<uint32_t> p2p_peer_dev;                           // per pack entry: the peer
+    dev_ptr<uint32_t *> p2p_signal_dev;                       // the neighbours' flags[this shard]
     uint32_t p2p_n_signal = 0;
     bool p2p_connected = false;
-    hvec<void *> p2p_retired;                          // receive sets / done counters of earlier plans, see p2p_release
+    hvec<dev_ptr<void>> p2p_retired;                   // receive sets / done counters of earlier plans, see p2p_release
     bool peer_run = false;                                    // the run in progress uses the peer form
     uint32_t p2p_epoch = 0;                                   // steps of peer-form runs done so far (tags and done counters)
     uint32_t p2p_spin_limit = 1u << 26;
@@ -306,15 +328,17 @@ struct snn_network {
     hipStream_t comm_stream = nullptr;
     hipEvent_t ev_packed = nullptr, ev_exchanged = nullptr;
 
-    hvec<void *> allocs;
-    std::map<void *, size_t> alloc_bytes;        // dev_alloc'ed arrays and their sizes (run_snapshot copies the small ones)
+    // the registry (dev_alloc, ascending address); the generation counts additions and removals
+    struct Registered { dev_ptr<void> mem; size_t bytes; bool scratch; };
+    hvec<Registered> registry;
+    uint64_t registry_generation = 0;
     // sparse form (CSR by local postsynaptic row); the arrays are replaced by every snn_set_graph_csr
     bool csr = false;
     uint64_t nnz = 0;
     // device: SELL-64 rows (slice_ptr / pre / w / row_len) + per-CSR-edge slot, local row and the transpose index
-    uint32_t *csr_ptr = nullptr, *csr_pre = nullptr, *csr_post = nullptr, *csr_t_ptr = nullptr, *csr_t_edge = nullptr;
-    uint32_t *csr_row_len = nullptr, *csr_edge_slot = nullptr;
-    float *csr_w = nullptr;
+    dev_ptr<uint32_t> csr_ptr, csr_pre, csr_post, csr_t_ptr, csr_t_edge;
+    dev_ptr<uint32_t> csr_row_len, csr_edge_slot;
+    dev_ptr<float> csr_w;
     uint64_t sell_entries = 0;
     hvec<uint32_t> edge_slot_host;   // CSR edge -> SELL entry (for snn_get_graph_csr)
     float *W = nullptr;
@@ -331,22 +355,22 @@ struct snn_network {
     // sparse shard handles: the spike-train cells the local rows read (ascending cell indices); the step iterates only
     // those -- cells are replicated state, and what this rank never reads it need not advance
     hvec<uint32_t> cell_list_host;
-    uint32_t *cell_list_dev = nullptr;
+    dev_ptr<uint32_t> cell_list_dev;
     uint32_t n_cells_listed = 0;
     // sparse handles: what the rows read of a cell, two copies (InputsArgs::st_view); rows read cell_view[cell_view_cur],
     // an iteration of the cells writes the other copy and flips
-    uint32_t *csr_plan = nullptr;            // gather plan of the row sums (SellGraph::plan), built from csr_pre
+    dev_ptr<uint32_t> csr_plan;              // gather plan of the row sums (SellGraph::plan), built from csr_pre
     // the step image (snn_kernels_csr.hpp, "STEP IMAGE"): headers + window pieces and the image's plan words are built on the
     // host with the graph; the records {plan word, weight} x 2 are packed on the device when the image is first needed and again
     // after anything changed a weight (img_stale)
-    uint32_t *csr_img_hdr = nullptr, *csr_plan_win = nullptr;
-    uint4 *csr_img_rec = nullptr;
+    dev_ptr<uint32_t> csr_img_hdr, csr_plan_win;
+    dev_ptr<uint4> csr_img_rec;
     uint64_t img_records = 0, img_staged_slices = 0;
     bool img_stale = true, csr_image = true;      // csr_image: option "csr_image"
     // ... and its twin for the runs of a shard handle whose rows gather the halo from the received segments (csr_plan_direct):
     // the same graph with every halo neuron's source moved to its word of the receive buffer; built with the exchange plan
-    uint32_t *csr_img_hdr_direct = nullptr, *csr_plan_win_direct = nullptr;
-    uint4 *csr_img_rec_direct = nullptr;
+    dev_ptr<uint32_t> csr_img_hdr_direct, csr_plan_win_direct;
+    dev_ptr<uint4> csr_img_rec_direct;
     uint64_t img_staged_slices_direct = 0;
     bool img_stale_direct = true;
     hvec<uint32_t> sell_pre_host, slice_ptr_host;     // the SELL indices as set (shard handles: the direct image is built from them)
@@ -369,7 +393,7 @@ struct snn_network {
     float *run_w_out = nullptr;           // STDP inside the one-launch run: where the workgroups leave their weights (layout of W)
     int persistent_stdp = 1;              // option "persistent_stdp"
     uint64_t stat_run_stdp_steps = 0;
-    uint32_t *run_failed = nullptr;       // hipHostMalloc: [0] a run gave up, [1] the co-residency probe said no
+    pinned_ptr<uint32_t> run_failed;      // hipHostMalloc: [0] a run gave up, [1] the co-residency probe said no
     uint32_t run_probed_grid = 0;         // grid size the probe last vouched for
     uint64_t stat_run_launches = 0, stat_run_steps = 0, stat_run_fallbacks = 0;
     uint64_t stat_run_external_stream = 0;      // run calls that kept one launch per step only because the handle runs on a caller's stream
@@ -386,7 +410,7 @@ struct snn_network {
     CopyEntry *snap_table = nullptr;
     uint32_t *snap_buf = nullptr;
     uint32_t snap_entries = 0, snap_max_words = 0;
-    size_t snap_allocs_seen = 0;
+    uint64_t snap_registry_seen = 0;     // registry_generation the table was laid out for
     size_t snap_words = 0;
     hvec<CopyEntry> snap_table_host;     // the table as uploaded (names of the arrays in a "verify" report)
     size_t verify_words = 0;                    // capacity of each half of verify_buf
@@ -396,12 +420,12 @@ struct snn_network {
     int verify = 0;
     uint32_t verify_fault = 0;                  // option "verify_fault" (test hook): word + 1 of the exchange buffer (2^30 + word of the weights) to disturb once
     uint32_t *verify_buf = nullptr;             // the first outcome, laid out like snap_buf
-    uint32_t *verify_report = nullptr;          // device words, see k_compare_table_alt
+    dev_ptr<uint32_t> verify_report;            // device words, see k_compare_table_alt
     int pinned_copies = 1;                      // option "pinned_copies" [1]: see copy_sync (SNN_AMD_PINNED_COPIES=0: the runtime stages pageable pointers itself)
-    void *copy_stage = nullptr;                 // its page-locked staging buffer (8 MiB, allocated with the first such copy)
-    uint32_t *verify_third = nullptr;           // on a mismatch: the second outcome, while a third execution decides which one repeats
+    pinned_ptr<char> copy_stage;                // its page-locked staging buffer (8 MiB, allocated with the first such copy)
+    dev_ptr<uint32_t> verify_third;             // on a mismatch: the second outcome, while a third execution decides which one repeats
     size_t verify_third_words = 0;
-    char *verify_big = nullptr;                 // runs with weight updates: [the matrices at the start | after the first pass]
+    dev_ptr<char> verify_big;                   // runs with weight updates: [the matrices at the start | after the first pass]
     size_t verify_big_bytes = 0;
     uint64_t snap_generation = 0;               // how often the snapshot table has been laid out
     uint64_t stat_verify_runs = 0, stat_verify_mismatches = 0, stat_verify_skipped = 0;
@@ -436,7 +460,7 @@ struct snn_network {
     float *stdp_dcol = nullptr, *stdp_drow = nullptr;
     uint32_t dcol_stride = 0;
     long long *st_clock_dev = nullptr;
-    long long *st_clock_pinned = nullptr;   // page-locked staging of st_clock for the asynchronous upload that opens a run
+    pinned_ptr<long long> st_clock_pinned;  // page-locked staging of st_clock for the asynchronous upload that opens a run
     long long run_step_offset = 0;
     bool run_active = false;        // a (possibly externally driven) run is open: device clocks are ahead of st_clock
     // fused small-lattice step (k_step_resident): two shadow copies of the exchange buffer + per-tile tickets
@@ -459,18 +483,18 @@ struct snn_network {
     int want_avg = 0, want_eeg = 0, want_counts = 0;
     // per-lattice weight snapshots (update_graph_history): [cap][count*count] per neuron lattice slot
     hvec<int> want_whist;
-    hvec<float *> whist;
+    hvec<dev_ptr<float>> whist;
     bool any_whist = false;
     float eeg_ref = 0.007f, eeg_dist = 0.8f, eeg_cond = 251.0f;     // EEGHistory defaults, neuron/mod.rs:246-255
-    float *summ_avg = nullptr, *summ_eeg = nullptr;                 // [cap][n_lattices]
+    dev_ptr<float> summ_avg, summ_eeg;                              // [cap][n_lattices]
     uint32_t *spike_counts = nullptr, *lat_first_dev = nullptr, *lat_count_dev = nullptr;
     uint64_t hist_steps = 0, hist_cap = 0;
     hvec<hvec<float>> preset_host;   // PresetSpikeTrain firing times per cell
-    float *preset_times_dev = nullptr;
+    dev_ptr<float> preset_times_dev;
     uint64_t hist_tick = 0;                // steps seen since the record was (re)started
     uint32_t hist_every = 1;               // a row is stored when hist_tick % hist_every == 0
-    float *vhist = nullptr, *st_vhist = nullptr;
-    unsigned long long *raster = nullptr;
+    dev_ptr<float> vhist, st_vhist;
+    dev_ptr<unsigned long long> raster;
 
     // synthetic drive (snn_set_synthetic_drive): off when drive_threshold == 0
     uint64_t drive_seed = 0;
@@ -524,6 +548,14 @@ inline hipError_t snn_malloc(T **out, size_t bytes)
     if (alloc_fault_now()) { *out = nullptr; return hipErrorOutOfMemory; }
     hipError_t e = hipMalloc(reinterpret_cast<void **>(out), bytes);
     return e != hipSuccess ? e : poison_if_asked(*out, bytes);
+}
+template <typename T>
+inline hipError_t snn_malloc(dev_ptr<T> *out, size_t bytes)
+{
+    T *p = nullptr;
+    const hipError_t e = snn_malloc(&p, bytes);
+    out->reset(p);
+    return e;
 }
 
 // Host <-> device transfers of the setters / getters and the fills of fresh buffers: on the HANDLE'S OWN stream, and waited
@@ -608,22 +640,62 @@ hipError_t alloc_streamed(void **out, size_t bytes)
     (void)hipGetLastError();
     return hipMalloc(out, bytes);
 }
+template <typename T>
+hipError_t alloc_streamed(dev_ptr<T> *out, size_t bytes)
+{
+    void *p = nullptr;
+    const hipError_t e = alloc_streamed(&p, bytes);
+    out->reset(static_cast<T *>(p));
+    return e;
+}
 
-int dev_alloc(snn_network *net, void **out, size_t bytes)
+// The registry owns the arrays dev_alloc hands out (the member pointers that name them do not) until the handle is destroyed or
+// dev_replace takes them out.  `scratch`: not state of the handle -- the snapshot's own buffers, verify's first outcome, the
+// one-launch run's granules, partials and phase clocks; run_snapshot and snn_debug_checkpoint copy every other entry.
+auto registry_slot(snn_network *net, const void *p)
+{
+    auto below = [](const snn_network::Registered &r, const void *q) { return std::less<const void *>()(r.mem.get(), q); };
+    return std::lower_bound(net->registry.begin(), net->registry.end(), p, below);
+}
+int dev_alloc(snn_network *net, void **out, size_t bytes, bool scratch = false)
 {
     *out = nullptr;
     if (bytes == 0) bytes = 256;
-    HIP_TRY(alloc_streamed(out, bytes), SNN_ERR_BUFFER_CREATE);
-    net->allocs.push_back(*out);
-    net->alloc_bytes[*out] = bytes;
-    HIP_TRY(poison_if_asked(*out, bytes), SNN_ERR_BUFFER_WRITE);
+    dev_ptr<void> mem;
+    HIP_TRY(alloc_streamed(&mem, bytes), SNN_ERR_BUFFER_CREATE);
+    void *const p = mem;
+    net->registry.insert(registry_slot(net, p), snn_network::Registered{std::move(mem), bytes, scratch});
+    net->registry_generation += 1;
+    *out = p;
+    HIP_TRY(poison_if_asked(p, bytes), SNN_ERR_BUFFER_WRITE);
     return SNN_OK;
 }
 
 template <typename T>
-int dev_alloc_t(snn_network *net, T **out, size_t count)
+int dev_alloc_t(snn_network *net, T **out, size_t count, bool scratch = false)
 {
-    return dev_alloc(net, reinterpret_cast<void **>(out), count * sizeof(T));
+    return dev_alloc(net, reinterpret_cast<void **>(out), count * sizeof(T), scratch);
+}
+
+// takes `old` out of the registry and returns its owner (freeing it unless kept); `fresh`, if given, takes its place and role
+dev_ptr<void> dev_replace(snn_network *net, const void *old, dev_ptr<void> fresh = nullptr)
+{
+    const auto it = registry_slot(net, old);
+    if (!old || it == net->registry.end() || it->mem.get() != old) return nullptr;
+    snn_network::Registered r = std::move(*it);
+    net->registry.erase(it);
+    if (fresh) {
+        void *const p = fresh;
+        net->registry.insert(registry_slot(net, p), snn_network::Registered{std::move(fresh), r.bytes, r.scratch});
+    }
+    net->registry_generation += 1;
+    return std::move(r.mem);
+}
+// size of a registered array, 0 if `p` is not one
+size_t dev_bytes(snn_network *net, const void *p)
+{
+    const auto it = registry_slot(net, p);
+    return (p && it != net->registry.end() && it->mem.get() == p) ? it->bytes : 0;
 }
 
 int fill_f32(snn_network *net, float *p, size_t n, float v)
@@ -898,7 +970,8 @@ int build_state(snn_network *net)
         TRY(fill_u32(net, net->spike_counts, np, 0));
     }
     net->want_whist.assign(nl, 0);
-    net->whist.assign(nl, nullptr);
+    net->whist.clear();
+    net->whist.resize(nl);
     net->stdp_host.assign(nl * PL_STRIDE, 0.0f);
     net->plast_host.assign(nl, 0);
     for (size_t l = 0; l < nl; ++l) {   // plasticity/mod.rs:29-39
@@ -1034,7 +1107,7 @@ int build_state(snn_network *net)
         TRY(fill_u32(net, c.lattice_slot + (l.first - net->nn), l.count, l.slot));
     net->st_clock.assign(std::max<size_t>(1, net->st_lattices.size()), 0);
     TRY(dev_alloc_t(net, &net->st_clock_dev, net->st_clock.size()));
-    HIP_TRY(host_malloc(reinterpret_cast<void **>(&net->st_clock_pinned), net->st_clock.size() * sizeof(long long), hipHostMallocDefault),
+    HIP_TRY(host_malloc(&net->st_clock_pinned, net->st_clock.size() * sizeof(long long), hipHostMallocDefault),
             SNN_ERR_BUFFER_CREATE);
 
     // graph + partials + counts

@@ -73,7 +73,7 @@ StdpArgs stdp_args(snn_network *net)
     a.flag = nullptr; a.dcol = net->stdp_dcol; a.drow = net->stdp_drow;
     a.dcol_stride = net->dcol_stride; a.n_lattices = (uint32_t)net->lattices.size();
     a.clock = net->clock;
-    a.conn_kind = net->any_conn_kind ? net->conn_kind_dev : nullptr;
+    a.conn_kind = net->any_conn_kind ? net->conn_kind_dev.get() : nullptr;
     a.st_lattice_slot = net->ca.lattice_slot;
     return a;
 }
@@ -611,33 +611,29 @@ int choose_matrix_placement(snn_network *net)
         net->profile = 0;
         float best_ms = 0.0f;
         int rc = time_input_pass(net, &best_ms);
-        // up to four more candidates; every loser stays allocated until the end so that each new candidate is
-        // forced into a different HBM region (a freed block would simply be handed out again)
-        hvec<void *> losers;
+        // up to four more candidates; every loser stays allocated until the end of the search (the end of this block) so that
+        // each new candidate is forced into a different HBM region (a freed block would simply be handed out again)
+        hvec<dev_ptr<void>> losers;
         for (int cand = 0; cand < 4 && rc == SNN_OK; ++cand) {
             size_t free_b = 0, total_b = 0;
-            void *b = nullptr;
+            dev_ptr<void> b;
             if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + (bytes >> 2) ||
                 alloc_streamed(&b, bytes) != hipSuccess)
                 break;
             float *a = net->W;
             float ms_b = 0.0f;
-            net->W = static_cast<float *>(b);
+            net->W = static_cast<float *>(b.get());
             rc = time_input_pass(net, &ms_b);
             if (getenv("SNN_DEBUG_PLACEMENT"))
-                fprintf(stderr, "[snn] matrix placement: held %p %.3f ms, candidate %p %.3f ms\n", (void *)a, best_ms, b, ms_b);
-            if (rc == SNN_OK && ms_b < best_ms * 0.99f) {       // the candidate wins
-                for (auto &p : net->allocs) if (p == a) p = b;
-                net->alloc_bytes.erase(a);
-                net->alloc_bytes[b] = bytes;
-                losers.push_back(a);
+                fprintf(stderr, "[snn] matrix placement: held %p %.3f ms, candidate %p %.3f ms\n", (void *)a, best_ms, b.get(), ms_b);
+            if (rc == SNN_OK && ms_b < best_ms * 0.99f) {       // the candidate wins: the registry holds it in place of the old one
+                losers.push_back(dev_replace(net, a, std::move(b)));
                 best_ms = ms_b;
             } else {
                 net->W = a;
-                losers.push_back(b);
+                losers.push_back(std::move(b));
             }
         }
-        for (void *p : losers) (void)hipFree(p);
         net->profile = prof;
         if (rc != SNN_OK) return rc;
     }
@@ -862,35 +858,30 @@ constexpr size_t RUN_PARTIAL_WORDS = (size_t)2 * RUN_RESIDENT_MAX_TILES * (RUN_R
 // [3][pad] block.  (Re)built when the handle has allocated since.
 int run_snapshot(snn_network *net, bool restore)
 {
-    if (!restore && (!net->snap_table || net->snap_allocs_seen != net->allocs.size())) {
+    if (!restore && (!net->snap_table || net->snap_registry_seen != net->registry_generation)) {
         const size_t limit = 4 * std::max<size_t>({(size_t)NUM_PLANES * net->xl.stride, (size_t)K_TYPES * net->n_pad,
                                                    (size_t)K_TYPES * net->c_pad, 256});
-        if (net->alloc_bytes.count(net->xbuf) == 0 || net->alloc_bytes[net->xbuf] > limit)
+        const size_t xbuf_bytes = dev_bytes(net, net->xbuf);
+        if (xbuf_bytes == 0 || xbuf_bytes > limit)
             return fail(SNN_ERR_BAD_STATE, "exchange buffer missing from the snapshot set");
         hvec<CopyEntry> table;
         size_t words = 0;
         uint32_t max_words = 0;
-        for (const auto &kv : net->alloc_bytes) {
-            if (kv.second > limit || kv.first == net->snap_table || kv.first == net->snap_buf ||
-                kv.first == net->run_granules || kv.first == net->run_partials || kv.first == net->run_timing || kv.first == net->verify_buf)
-                continue;
-            const uint32_t w = (uint32_t)(kv.second / 4);
+        for (const auto &r : net->registry) {
+            if (r.scratch || r.bytes > limit) continue;
+            const uint32_t w = (uint32_t)(r.bytes / 4);
             // pad = 1: contents depend on the order of atomics (the compacted spike list) -- copied, but not compared by "verify"
-            table.push_back(CopyEntry{static_cast<uint32_t *>(kv.first), nullptr, w, kv.first == (void *)net->spike_list ? 1u : 0u});
+            table.push_back(CopyEntry{static_cast<uint32_t *>(r.mem.get()), nullptr, w, r.mem.get() == (void *)net->spike_list ? 1u : 0u});
             words += w;
             max_words = std::max(max_words, w);
         }
         // (the two buffers are replaced, not grown: a handle allocates a handful of times in its life)
-        for (void *old : {(void *)net->snap_table, (void *)net->snap_buf})
-            if (old) {
-                (void)hipFree(old);
-                net->alloc_bytes.erase(old);
-                net->allocs.erase(std::remove(net->allocs.begin(), net->allocs.end(), old), net->allocs.end());
-            }
+        dev_replace(net, net->snap_table);
+        dev_replace(net, net->snap_buf);
         net->snap_table = nullptr; net->snap_buf = nullptr;
-        TRY(dev_alloc_t(net, &net->snap_buf, words));
+        TRY(dev_alloc_t(net, &net->snap_buf, words, /*scratch=*/true));
         net->snap_words = words;
-        TRY(dev_alloc_t(net, &net->snap_table, table.size()));
+        TRY(dev_alloc_t(net, &net->snap_table, table.size(), /*scratch=*/true));
         size_t off = 0;
         for (auto &e : table) { e.dst = net->snap_buf + off; off += e.words; }
         HIP_TRY(hipMemcpyAsync(net->snap_table, table.data(), table.size() * sizeof(CopyEntry), hipMemcpyHostToDevice, net->stream),
@@ -900,7 +891,7 @@ int run_snapshot(snn_network *net, bool restore)
         net->snap_generation += 1;
         net->snap_entries = (uint32_t)table.size();
         net->snap_max_words = max_words;
-        net->snap_allocs_seen = net->allocs.size();
+        net->snap_registry_seen = net->registry_generation;
     }
     if (!net->snap_entries) return SNN_OK;
     const uint32_t bx = std::max(1u, std::min(16u, (net->snap_max_words + 1023u) / 1024u));
@@ -912,11 +903,11 @@ int run_snapshot(snn_network *net, bool restore)
 int launch_run_resident(snn_network *net, uint64_t iterations, uint64_t steps_before = 0)
 {
     if (!net->run_granules) {
-        TRY(dev_alloc_t(net, &net->run_granules, RUN_GRANULE_WORDS));
+        TRY(dev_alloc_t(net, &net->run_granules, RUN_GRANULE_WORDS, /*scratch=*/true));
         HIP_TRY(hipMemsetAsync(net->run_granules, 0, RUN_GRANULE_WORDS * 8, net->stream), SNN_ERR_BUFFER_WRITE);
-        TRY(dev_alloc_t(net, &net->run_partials, RUN_PARTIAL_WORDS));
+        TRY(dev_alloc_t(net, &net->run_partials, RUN_PARTIAL_WORDS, /*scratch=*/true));
         HIP_TRY(hipMemsetAsync(net->run_partials, 0, RUN_PARTIAL_WORDS * 8, net->stream), SNN_ERR_BUFFER_WRITE);
-        HIP_TRY(host_malloc(reinterpret_cast<void **>(&net->run_failed), 8, hipHostMallocMapped), SNN_ERR_BUFFER_CREATE);
+        HIP_TRY(host_malloc(&net->run_failed, 8, hipHostMallocMapped), SNN_ERR_BUFFER_CREATE);
         net->run_failed[0] = net->run_failed[1] = 0u;
         net->run_tag = 1;
     }
@@ -968,7 +959,7 @@ int launch_run_resident(snn_network *net, uint64_t iterations, uint64_t steps_be
         r.view_clock0 = net->clock;
         r.st_vhist_row = (recording(net) && net->want_vhist && net->st_vhist) ? net->st_vhist + (size_t)net->hist_steps * net->c_pad : nullptr;
         r.st_vhist_stride = net->c_pad;
-        if (!net->run_timing && (net->run_timing_opt || getenv("SNN_AMD_RUN_TIMING"))) TRY(dev_alloc_t(net, &net->run_timing, (size_t)RUN_RESIDENT_MAX_TILES * RUN_RESIDENT_MAX_GROUPS * 4));
+        if (!net->run_timing && (net->run_timing_opt || getenv("SNN_AMD_RUN_TIMING"))) TRY(dev_alloc_t(net, &net->run_timing, (size_t)RUN_RESIDENT_MAX_TILES * RUN_RESIDENT_MAX_GROUPS * 4, /*scratch=*/true));
         r.timing = net->run_timing;
         // chemical synapses: the transmitter types some NEURON releases travel (cells with transmitters keep the per-step forms)
         if (net->chemical)
@@ -1369,25 +1360,24 @@ int grow_history(snn_network *net, uint64_t extra)
         if (ok) return SNN_OK;
     }
     const uint64_t cap = std::max<uint64_t>(need, net->hist_cap + net->hist_cap / 2);   // geometric: O(T) copies overall
-    auto regrow = [&](void **buf, size_t row_bytes, bool wanted) -> int {
+    auto regrow = [&](auto &buf, size_t row_bytes, bool wanted) -> int {
         if (!wanted || row_bytes == 0) return SNN_OK;
-        void *nb = nullptr;
+        std::remove_reference_t<decltype(buf)> nb;
         HIP_TRY(snn_malloc(&nb, std::max<size_t>(256, cap * row_bytes)), SNN_ERR_BUFFER_CREATE);
-        if (*buf && net->hist_steps)
-            HIP_TRY(hipMemcpyAsync(nb, *buf, net->hist_steps * row_bytes, hipMemcpyDeviceToDevice, net->stream),
+        if (buf && net->hist_steps)
+            HIP_TRY(hipMemcpyAsync(nb, buf, net->hist_steps * row_bytes, hipMemcpyDeviceToDevice, net->stream),
                     SNN_ERR_BUFFER_WRITE);
         HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
-        if (*buf) (void)hipFree(*buf);
-        *buf = nb;
+        buf = std::move(nb);
         return SNN_OK;
     };
-    TRY(regrow(reinterpret_cast<void **>(&net->vhist), (size_t)net->n_pad * 4, net->want_vhist));
-    TRY(regrow(reinterpret_cast<void **>(&net->st_vhist), (size_t)net->c_pad * 4, net->want_vhist));
-    TRY(regrow(reinterpret_cast<void **>(&net->raster), (size_t)(net->n_pad / 64) * 8, net->want_raster));
-    TRY(regrow(reinterpret_cast<void **>(&net->summ_avg), net->lattices.size() * 4, net->want_avg));
-    TRY(regrow(reinterpret_cast<void **>(&net->summ_eeg), net->lattices.size() * 4, net->want_eeg));
+    TRY(regrow(net->vhist, (size_t)net->n_pad * 4, net->want_vhist));
+    TRY(regrow(net->st_vhist, (size_t)net->c_pad * 4, net->want_vhist));
+    TRY(regrow(net->raster, (size_t)(net->n_pad / 64) * 8, net->want_raster));
+    TRY(regrow(net->summ_avg, net->lattices.size() * 4, net->want_avg));
+    TRY(regrow(net->summ_eeg, net->lattices.size() * 4, net->want_eeg));
     for (const auto &l : net->lattices)
-        TRY(regrow(reinterpret_cast<void **>(&net->whist[l.slot]), (size_t)l.count * l.count * 4, net->want_whist[l.slot] != 0));
+        TRY(regrow(net->whist[l.slot], (size_t)l.count * l.count * 4, net->want_whist[l.slot] != 0));
     net->hist_cap = cap;
     net->stat_history_regrows += 1;
     return SNN_OK;
@@ -1477,20 +1467,13 @@ int graph_rows_io(snn_network *net, uint32_t pre_begin, uint32_t pre_count, floa
     // <= 64 MiB of host rows per hop and <= 32768 rows (grid.y of the import / export kernels)
     const uint32_t hop = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(pre_count, 32768),
                                                                         (64u << 20) / (host_ld * 4)));
-    float *dw = nullptr;
-    uint32_t *dc = nullptr;
+    dev_ptr<float> dw;
+    dev_ptr<uint32_t> dc, bad;
     HIP_TRY(snn_malloc(&dw, (size_t)hop * host_ld * 4), SNN_ERR_BUFFER_CREATE);
-    if (snn_malloc(&dc, (size_t)hop * host_ld * 4) != hipSuccess) {
-        (void)hipFree(dw);
-        return fail(SNN_ERR_BUFFER_CREATE, "staging allocation failed");
-    }
+    if (snn_malloc(&dc, (size_t)hop * host_ld * 4) != hipSuccess) return fail(SNN_ERR_BUFFER_CREATE, "staging allocation failed");
     int rc = SNN_OK;
-    uint32_t *bad = nullptr;
-    if (set && (snn_malloc(&bad, 256) != hipSuccess || hipMemsetAsync(bad, 0, 256, net->stream) != hipSuccess)) {
-        (void)hipFree(dw); (void)hipFree(dc);
-        if (bad) (void)hipFree(bad);
+    if (set && (snn_malloc(&bad, 256) != hipSuccess || hipMemsetAsync(bad, 0, 256, net->stream) != hipSuccess))
         return fail(SNN_ERR_BUFFER_CREATE, "staging allocation failed");
-    }
     for (uint32_t r = 0; r < pre_count && rc == SNN_OK; r += hop) {
         const uint32_t rows = std::min(hop, pre_count - r);
         const size_t bytes = (size_t)rows * host_ld * 4;
@@ -1523,9 +1506,6 @@ int graph_rows_io(snn_network *net, uint32_t pre_begin, uint32_t pre_count, floa
     }
     uint32_t bad_host[3] = {0, 0, 0};
     if (set && rc == SNN_OK && copy_sync(net, bad_host, bad, 12, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SNN_ERR_BUFFER_READ, "graph check download failed");
-    (void)hipFree(dw);
-    (void)hipFree(dc);
-    if (bad) (void)hipFree(bad);
     if (set) net->counts_dirty = true;
     if (rc == SNN_OK && bad_host[0])
         return fail(SNN_ERR_BAD_ARG, std::to_string(bad_host[0]) + " connected edge(s) carry a NaN weight, e.g. (pre " + std::to_string(bad_host[1]) +

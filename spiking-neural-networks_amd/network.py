@@ -179,9 +179,9 @@ class DeviceNetwork:
         w = np.ascontiguousarray(weights, dtype=np.float32)
         if rp.size != sum(e - b for b, e in self.ranges) + 1 or pi.size != w.size:
             raise ValueError("row_ptr must have one entry per owned neuron + 1 and pre_index / weights equal lengths")
-        self._nnz = int(w.size)
         self._check(self._L.snn_set_graph_csr(self._h, rp.ctypes.data_as(_lib.u64p), pi.ctypes.data_as(_lib.u32p),
                                              w.ctypes.data_as(_lib.f32p), w.size))
+        self._nnz = int(w.size)                  # (a failed call leaves the previous graph in place)
 
     def get_graph_csr(self):
         w = _out(getattr(self, "_nnz", 0), np.float32)

@@ -106,6 +106,48 @@ def test_every_allocation_of_a_sequence_may_fail(snn, name):
         arm(snn, 0)
 
 
+def test_a_failed_sparse_graph_replacement_keeps_the_previous_graph(snn):
+    """snn_set_graph_csr is all or nothing: whichever allocation of the call fails, the handle still holds graph A -- its weights
+    read back bit for bit and its next steps are the oracle's steps of A"""
+    case = CASES["sparse"]
+    steps_before, steps_after = 4, 3
+    net_a, net_b = make_oracle(case, 11), make_oracle(case, 23)
+
+    def handle_on_a():
+        dn = parity.device_from_oracle(snn, net_a, csr=True)
+        dn.run(steps_before)
+        return dn
+
+    try:
+        dn = handle_on_a()
+        graph_b = parity.csr_for_posts(net_b, dn.owned)
+        before = arm(snn, 0)
+        dn.set_graph_csr(*graph_b)
+        total = arm(snn, 0) - before
+        dn.close()
+        assert total > 10, f"only {total} allocations counted in snn_set_graph_csr"
+        onet = make_oracle(case, 11)
+        onet.run(steps_before + steps_after)
+        for n in range(1, total + 1):
+            dn = handle_on_a()
+            try:
+                w_a = dn.get_graph_csr()
+                arm(snn, n)
+                with pytest.raises(snn.SnnError) as failed:
+                    dn.set_graph_csr(*graph_b)
+                arm(snn, 0)
+                assert failed.value.code in (3, 4, 5, 6, 8, 12), (n, total, str(failed.value))
+                assert np.array_equal(dn.get_graph_csr().view(np.uint32), w_a.view(np.uint32)), (n, total)
+                dn.run(steps_after)
+                v = dn.get_attr(0, "current_voltage")
+                assert np.array_equal(v.view(np.uint32), onet["current_voltage"][:v.size].view(np.uint32)), (n, total)
+            finally:
+                arm(snn, 0)
+                dn.close()
+    finally:
+        arm(snn, 0)
+
+
 def test_a_handle_that_failed_half_way_is_still_a_handle(snn):
     """after a failed finalize / run the handle answers further calls with status codes and can be destroyed"""
     case = CASES["dense"]
