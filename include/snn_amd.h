@@ -647,8 +647,9 @@ int snn_probe_math(int device, int which, const float *in, float *out, size_t co
 
 /* The same over a range of binary32 BIT PATTERNS formed on the device: out[i] = f(x_i), x_i = the float with bits
  * first + i * stride (mod 2^32); which = 3 evaluates powf(x_i, y) (generated models, `x ^ n`); which = 4, 5, 6 = exp, pow3, pow4
- * through the branch-free main paths with the full function as fall-back (the form of the Hodgkin-Huxley step).  The GPU parity
- * test walks all 2^32 patterns with it. */
+ * through the branch-free main paths with the full function as fall-back (the form of the Hodgkin-Huxley step); which = 7 .. 12 =
+ * tanh, sinh, cosh, sin, cos, tan as generated models evaluate them (`tanh(...)`, `sin(...)` ... of a description).  The GPU
+ * parity test walks all 2^32 patterns of every selector but 3 with it. */
 int snn_probe_math_bits(int device, int which, uint32_t first, uint32_t stride, float y, float *out, size_t count);
 
 #ifdef __cplusplus

@@ -99,17 +99,47 @@ float snn_o_cosf_export(float x) { return snn_o_cosf(x); }
 float snn_o_tanf_export(float x) { return snn_o_tanf(x); }
 float snn_o_powf_export(float x, float y) { return snn_o_powf(x, y); }
 
-/* out[i] = f(the float whose bit pattern is first + i * stride): which = 0 expf, 1 powf(x, 3.), 2 powf(x, 4.),
- * 3 powf(x, y).  All cores; the GPU parity test walks the whole 2^32 pattern space in chunks with it. */
-void snn_o_math_bits(int which, uint32_t first, uint32_t stride, uint64_t count, float y, float *out)
+/* one value of function `which`: 0 expf, 1 powf(x, 3.), 2 powf(x, 4.), 3 powf(x, y); 4, 5, 6 are the device's branch-free
+ * forms of 0, 1, 2 and have the same values; 7 .. 12 tanh, sinh, cosh, sin, cos, tan of generated models.  The caller has
+ * checked the selector (o_math_known). */
+static inline float o_math_one(int which, float x, float y)
 {
+    switch (which) {
+    case 0: case 4: return snn_o_expf(x);
+    case 1: case 5: return snn_o_pow3f(x);
+    case 2: case 6: return snn_o_pow4f(x);
+    case 3: return snn_o_powf(x, y);
+    case 7: return snn_o_tanhf(x);
+    case 8: return snn_o_sinhf(x);
+    case 9: return snn_o_coshf(x);
+    case 10: return snn_o_sinf(x);
+    case 11: return snn_o_cosf(x);
+    default: return snn_o_tanf(x);
+    }
+}
+static int o_math_known(int which) { return which >= 0 && which <= 12; }
+
+/* out[i] = f(the float whose bit pattern is first + i * stride), f as in o_math_one.  Returns 0, or -1 for an unknown
+ * selector (nothing written).  All cores; the GPU parity test walks the whole 2^32 pattern space in chunks with it. */
+int snn_o_math_bits(int which, uint32_t first, uint32_t stride, uint64_t count, float y, float *out)
+{
+    if (!o_math_known(which)) return -1;
     /* (a handful of values is evaluated by the caller's thread: a team of as many threads as the box shows CPUs -- 256 on the
      * GPU boxes, of which a container may use 16 -- costs tens of milliseconds per region once the cores are oversubscribed) */
 #pragma omp parallel for schedule(static) if (count >= 4096)
-    for (uint64_t i = 0; i < count; i++) {
-        const float x = snn_o_asfloat(first + (uint32_t)i * stride);
-        out[i] = which == 0 ? snn_o_expf(x) : which == 1 ? snn_o_pow3f(x) : which == 2 ? snn_o_pow4f(x) : snn_o_powf(x, y);
-    }
+    for (uint64_t i = 0; i < count; i++)
+        out[i] = o_math_one(which, snn_o_asfloat(first + (uint32_t)i * stride), y);
+    return 0;
+}
+
+/* the same for an array of bit patterns, result bit patterns out: out_bits[i] = bits of f(float with bits in_bits[i]) */
+int snn_o_math_array(int which, const uint32_t *in_bits, uint64_t count, float y, uint32_t *out_bits)
+{
+    if (!o_math_known(which)) return -1;
+#pragma omp parallel for schedule(static) if (count >= 4096)
+    for (uint64_t i = 0; i < count; i++)
+        out_bits[i] = snn_o_asuint(o_math_one(which, snn_o_asfloat(in_bits[i]), y));
+    return 0;
 }
 
 /* ---------- synthetic data ---------- */

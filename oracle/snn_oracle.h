@@ -297,7 +297,9 @@ float snn_o_sinf_export(float x);
 float snn_o_cosf_export(float x);
 float snn_o_tanf_export(float x);
 float snn_o_powf_export(float x, float y);
-void snn_o_math_bits(int which, uint32_t first, uint32_t stride, uint64_t count, float y, float *out);
+/* which = 0 expf, 1 powf(x, 3.), 2 powf(x, 4.), 3 powf(x, y), 4-6 as 0-2, 7 .. 12 tanh, sinh, cosh, sin, cos, tan; -1 for any other */
+int snn_o_math_bits(int which, uint32_t first, uint32_t stride, uint64_t count, float y, float *out);
+int snn_o_math_array(int which, const uint32_t *in_bits, uint64_t count, float y, uint32_t *out_bits);
 float snn_o_stdp_delta(int32_t t_pre, int32_t t_post, float a_plus, float a_minus,
                        float tau_plus, float tau_minus, float dt);
 float snn_o_exponential_decay_effect(int64_t timestep, int32_t last_firing_time,

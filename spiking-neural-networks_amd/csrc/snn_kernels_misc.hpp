@@ -717,12 +717,18 @@ __global__ void k_probe_math(int which, const float *in, float *out, size_t n)
     out[i] = which == 0 ? expf_glibc(x) : (which == 1 ? pow3f_glibc(x) : pow4f_glibc(x));
 }
 
-// the same over a range of float bit patterns generated on the device: x = asfloat(first + i * stride); which = 3: powf(x, y)
+// the same over a range of float bit patterns generated on the device: x = asfloat(first + i * stride); which = 3: powf(x, y);
+// 7..12: tanh, sinh, cosh, sin, cos, tan as generated model code calls them
 __global__ void k_probe_math_bits(int which, uint32_t first, uint32_t stride, float y, float *out, size_t n)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float x = __uint_as_float(first + (uint32_t)i * stride);
+    if (which >= 7) {
+        out[i] = which == 7 ? tanhf_portable(x) : which == 8 ? sinhf_portable(x) : which == 9 ? coshf_portable(x)
+               : which == 10 ? sinf_portable(x) : which == 11 ? cosf_portable(x) : tanf_portable(x);
+        return;
+    }
     if (which >= 4) {
         // the form the Hodgkin-Huxley step uses: the branch-free main path, the full function where that one says "special"
         bool special = false;

@@ -593,7 +593,8 @@ def probe_math(which, x, device=0):
 
 
 def probe_math_bits(which, first, count, stride=1, y=0.0, device=0):
-    """The same over float BIT PATTERNS first + i * stride formed on the device; which = 3: powf(x, y)."""
+    """The same over float BIT PATTERNS first + i * stride formed on the device; which = 3: powf(x, y), 4-6: the
+    branch-free forms of 0-2, 7-12: tanh, sinh, cosh, sin, cos, tan of generated models."""
     L = _lib.load()
     out = _out(count, np.float32)
     _lib.check(L.snn_probe_math_bits(device, which, first & 0xFFFFFFFF, stride, float(y), out.ctypes.data_as(_lib.f32p),

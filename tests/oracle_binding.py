@@ -142,7 +142,9 @@ def lib():
         L.snn_o_powf_export.argtypes = [C.c_float, C.c_float]
         L.snn_o_powf_export.restype = C.c_float
         L.snn_o_math_bits.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_float, C.POINTER(C.c_float)]
-        L.snn_o_math_bits.restype = None
+        L.snn_o_math_bits.restype = C.c_int
+        L.snn_o_math_array.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.c_uint64, C.c_float, C.POINTER(C.c_uint32)]
+        L.snn_o_math_array.restype = C.c_int
         L.snn_o_stdp_delta.argtypes = [C.c_int32, C.c_int32] + [C.c_float] * 5
         L.snn_o_stdp_delta.restype = C.c_float
         L.snn_o_delta_dirac_effect.argtypes = [C.c_int64, C.c_int32] + [C.c_float] * 4
@@ -544,9 +546,25 @@ def powf(x, y):
 
 
 def math_bits(which, first, count, stride=1, y=0.0):
-    """f(float with bit pattern first + i * stride), i < count: which = 0 expf, 1 powf(x, 3), 2 powf(x, 4), 3 powf(x, y)"""
+    """f(float with bit pattern first + i * stride), i < count: which = 0 expf, 1 powf(x, 3), 2 powf(x, 4), 3 powf(x, y),
+    4-6 the same values as 0-2 (other device forms), 7 .. 12 tanh, sinh, cosh, sin, cos, tan; any other is an error"""
     out = np.empty(count, np.float32)
-    lib().snn_o_math_bits(which, first & 0xFFFFFFFF, stride, count, float(y), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if lib().snn_o_math_bits(which, first & 0xFFFFFFFF, stride, count, float(y), out.ctypes.data_as(C.POINTER(C.c_float))):
+        raise ValueError(f"unknown function selector {which}")
+    return out
+
+
+MATH_SELECTORS = {"expf": 0, "pow3": 1, "pow4": 2, "powf": 3, "tanhf": 7, "sinhf": 8, "coshf": 9, "sinf": 10, "cosf": 11,
+                  "tanf": 12}
+
+
+def math_array(which, bits, y=0.0):
+    """bit patterns of f(x) for an array of binary32 bit patterns of x (uint32 in, uint32 out); selectors as math_bits"""
+    bits = np.ascontiguousarray(bits, np.uint32)
+    out = np.empty(bits.shape, np.uint32)
+    if lib().snn_o_math_array(which, bits.ctypes.data_as(C.POINTER(C.c_uint32)), bits.size, float(y),
+                              out.ctypes.data_as(C.POINTER(C.c_uint32))):
+        raise ValueError(f"unknown function selector {which}")
     return out
 
 

@@ -1,7 +1,9 @@
 """The stepper's device functions (expf, powf(x, 3.), powf(x, 4.), powf -- csrc/snn_math.hpp) against the oracle's, on
 the GPU: bit-identical on EVERY binary32 input (all 2^32 bit patterns each for expf / pow3 / pow4, walked in chunks),
 so transcendental-bearing models (HH, NMDA, Destexhe, STDP, DeltaDirac) are held to the same bit-exact bar as the
-Izhikevich path.  The oracle's functions are in turn pinned to glibc's libm on all 2^32 inputs (test_oracle_math.py)."""
+Izhikevich path.  The oracle's functions are in turn pinned to glibc's libm on all 2^32 inputs (test_oracle_math.py).
+The same walk for tanh / sinh / cosh / sin / cos / tan of generated models: those the oracle holds to the exact value
+(a committed mpmath fixture) and measures against glibc on all 2^32 inputs, also in test_oracle_math.py."""
 import numpy as np
 import pytest
 
@@ -16,15 +18,33 @@ def same_bits(a, b):
     return bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
 
 
-@pytest.mark.parametrize("which", [0, 1, 2, 4, 5, 6], ids=["expf", "pow3", "pow4", "expf_main_path", "pow3_main_path", "pow4_main_path"])
-def test_every_binary32_input_bit_identical(snn, which):
+def walk_all_patterns(snn, which):
+    """device = oracle on all 2^32 bit patterns of selector `which` (the oracle knows 4, 5, 6 as the values of 0, 1, 2):
+    NaN against NaN passes, everything else -- signed zeros, infinities, subnormal results -- by bits"""
     for first in range(0, 1 << 32, CHUNK):
         got = snn.probe_math_bits(which, first, CHUNK)
-        want = ob.math_bits(which % 4 if which >= 4 else which, first, CHUNK)     # (4, 5, 6 are other device forms of 0, 1, 2)
+        want = ob.math_bits(which, first, CHUNK)
         if not same_bits(got, want):
-            bad = np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))[:5]
+            gb, wb = got.view(np.uint32), want.view(np.uint32)
+            bad = np.flatnonzero((gb != wb) & ~(np.isnan(got) & np.isnan(want)))[:5]
             raise AssertionError(f"function {which}: bit patterns {[hex(first + int(i)) for i in bad]} differ: "
-                                 f"device {got[bad]}, oracle {want[bad]}")
+                                 f"device {got[bad]} {[hex(int(v)) for v in gb[bad]]}, "
+                                 f"oracle {want[bad]} {[hex(int(v)) for v in wb[bad]]}")
+
+
+@pytest.mark.parametrize("which", [0, 1, 2, 4, 5, 6], ids=["expf", "pow3", "pow4", "expf_main_path", "pow3_main_path", "pow4_main_path"])
+def test_every_binary32_input_bit_identical(snn, which):
+    walk_all_patterns(snn, which)
+
+
+@pytest.mark.parametrize("which", [7, 8, 9, 10, 11, 12], ids=["tanh", "sinh", "cosh", "sin", "cos", "tan"])
+def test_every_binary32_input_of_generated_model_functions_bit_identical(snn, which):
+    """tanhf_portable .. tanf_portable, what modelgen emits for `tanh(...)` .. `tan(...)` of a description: every crossover
+    of the hyperbolic functions, every multiple of pi/2 a float comes near, and the circular functions far outside the
+    range where their reduction is accurate (|x| >= 2^20 * pi/2 -- there the values are wrong but must still be the
+    oracle's: the quadrant is read from the bit pattern of x * 2/pi + 1.5 * 2^52, defined for every x on both sides, and
+    tan rests on the device's binary64 division being correctly rounded)."""
+    walk_all_patterns(snn, which)
 
 
 @pytest.mark.parametrize("y", [5.0, 7.0, -2.0, -3.0, 0.5, 2.5])
