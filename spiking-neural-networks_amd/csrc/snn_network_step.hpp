@@ -3,9 +3,41 @@
 // histories, HBM placement of the synapse matrix, run bookkeeping and dense graph transfers.
 // Included by snn_network.hip only (one translation unit).
 #pragma once
+#include "snn_dispatch.hpp"
 #include "snn_network_state.hpp"
 
 namespace {
+
+// The profiler's bracket (snn_profile_*): a pair of HIP events from the handle's pool around the launches that stream the graph --
+// counted as `passes` passes over it -- or, from a pool of its own, around the step's weight updates.  *e1 stays null while
+// profiling is off; profile_close records it.
+enum ProfilePool { PROFILE_GRAPH_PASS, PROFILE_PLASTICITY };
+int profile_open(snn_network *net, ProfilePool which, int passes, hipEvent_t *e1)
+{
+    *e1 = nullptr;
+    if (!net->profile) return SNN_OK;
+    auto &pool = which == PROFILE_PLASTICITY ? net->ev_pool_pl : net->ev_pool;
+    size_t &used = which == PROFILE_PLASTICITY ? net->ev_used_pl : net->ev_used;
+    if (used == pool.size()) {
+        hipEvent_t x, y;
+        HIP_TRY(hipEventCreate(&x), SNN_ERR_QUEUE);
+        HIP_TRY(hipEventCreate(&y), SNN_ERR_QUEUE);
+        pool.emplace_back(x, y);
+    }
+    if (which == PROFILE_GRAPH_PASS) {
+        net->ev_counts.resize(pool.size(), 1);
+        net->ev_counts[used] = passes;
+    }
+    const auto ev = pool[used++];
+    *e1 = ev.second;
+    HIP_TRY(hipEventRecord(ev.first, net->stream), SNN_ERR_QUEUE);
+    return SNN_OK;
+}
+int profile_close(snn_network *net, hipEvent_t e1)
+{
+    if (e1) HIP_TRY(hipEventRecord(e1, net->stream), SNN_ERR_QUEUE);
+    return SNN_OK;
+}
 
 // Arguments of the cells' job (k_spike_trains, or the cell blocks of k_step_csr / k_step_close); returns the number of
 // threads it needs.  iterate = 1 flips the sparse handles' view: the launch writes the copy the NEXT input calculation reads.
@@ -89,6 +121,77 @@ void local_chunks(const snn_network *net, uint32_t *begin, uint32_t *count)
     *count = ce > cb ? ce - cb : 0;
 }
 
+// the dense input pass in one of its three forms: applying the STDP update the previous step deferred, applying its
+// reward-modulated update, or plain
+int launch_inputs_dense(snn_network *net, InputsPart part, InputsArgs &a, uint32_t grid_chunks)
+{
+    // shape of the pass: cache-resident matrices take the latency-oriented one-wave shape; streamed matrices the
+    // 4-columns-per-lane shape, or the 2-column shape while that would leave the chip under-filled
+    const bool resident = (size_t)net->n_tot * net->ld * 4 <= ((size_t)64 << 20);
+    const uint64_t waves4 = (uint64_t)((net->n_loc + 255) / 256) * grid_chunks;
+    // same-box A/B of the two streamed shapes (profiles/ab_input_shape.py, profiles/r03/ab_input_shape_by_size.txt): the
+    // 2-column shape wins by 0.8 - 2.4 % from 96x96 to 240x240 (waves4 up to 50 625), the 4-column shape by 0.5 % at 256x256
+    int shape = resident ? 0 : (waves4 < 57600 ? 2 : 1);
+    if (net->force_shape > 0 && !resident) shape = net->force_shape;     // SNN_AMD_INPUT_SHAPE=1|2 (experiments)
+    if (net->rstdp_pending && part != INPUTS_ALL) TRY(flush_rstdp(net));
+    const bool stdp_fused = !LEAN_INPUT_PASS && net->stdp_pending && !net->rstdp_pending && part == INPUTS_ALL && shape != 0;
+    if (net->stdp_pending && !stdp_fused) TRY(flush_stdp(net));
+    // launch(grid, block) in the geometry of shape SH
+    auto in_shape = [&](auto SH, auto launch) {
+        using S = InputsShape<decltype(SH)::value>;
+        launch(dim3((net->n_loc + S::TILE - 1) / S::TILE, grid_chunks), dim3(S::THREADS));
+    };
+    if (stdp_fused) {
+        // the STDP update of the previous step rides on this pass over W
+        net->stdp_pending = false;
+        const bool rows_only = net->stdp_pending_rows_only;
+        net->stdp_pending_rows_only = false;
+        a.W_rw = net->W; a.stdp_count = net->spike_count; a.stdp_flag = net->stdp_flag;
+        a.stdp_dcol = net->stdp_dcol; a.stdp_drow = net->stdp_drow; a.lattice_slot = net->lattice_slot;
+        a.dcol_stride = net->dcol_stride; a.n_lattices = (uint32_t)net->lattices.size();
+        a.stdp_rowbits = net->stdp_rowbits;
+        for (int k = 0; k < K_TYPES; ++k) a.live_type[k] = (uint32_t)k;     // the generic three-slot chemical variant
+        for_synapses(net->electrical, net->chemical, [&](auto E, auto C) {
+            if constexpr (!LEAN_INPUT_PASS)
+                for_value<1, 2>(shape, [&](auto SH) {
+                    in_shape(SH, [&](dim3 grid, dim3 block) {
+                        if (rows_only) hipLaunchKernelGGL((k_inputs_dense<E(), C(), SH(), K_TYPES, 2>), grid, block, 0, net->stream, a);
+                        else hipLaunchKernelGGL((k_inputs_dense<E(), C(), SH(), K_TYPES, 1>), grid, block, 0, net->stream, a);
+                    });
+                });
+        });
+    } else if (net->rstdp_pending) {
+        // the reward-modulated weight update of the previous step rides on this pass over W
+        net->rstdp_pending = false;
+        RstdpInputsArgs ra{};
+        ra.in = a; ra.W = net->W; ra.C = net->trace;
+        ra.last_firing_time = net->na.last_firing_time; ra.lattice_slot = net->lattice_slot;
+        ra.rm = net->rm_dev; ra.rm_on = net->rm_on_dev;
+        ra.dop = net->reward_since_defer ? RM_DOPAMINE_BEFORE : RM_DOPAMINE;
+        for_synapses(net->electrical, net->chemical, [&](auto E, auto C) {
+            for_value<1, 2, 0>(shape, [&](auto SH) {
+                in_shape(SH, [&](dim3 grid, dim3 block) {
+                    hipLaunchKernelGGL((k_inputs_rstdp<E(), C(), SH()>), grid, block, 0, net->stream, ra);
+                });
+            });
+        });
+    } else {
+        // chemical synapses: the pass specialised on the number of live transmitter types
+        if (LEAN_INPUT_PASS && net->chemical)
+            for (int k = 0; k < K_TYPES; ++k) a.live_type[k] = (uint32_t)k;
+        for_synapses(net->electrical, net->chemical, [&](auto E, auto C) {
+            for_value<1, 2, 0>(shape, [&](auto SH) {
+                in_shape(SH, [&](dim3 grid, dim3 block) {
+                    auto pass = [&](auto NT) { hipLaunchKernelGGL((k_inputs_dense<E(), C(), SH(), NT()>), grid, block, 0, net->stream, a); };
+                    if constexpr (!C() || LEAN_INPUT_PASS) pass(int_c<3>{});
+                    else for_value<1, 2, 3>((int)net->n_live, pass);
+                });
+            });
+        });
+    }
+    return SNN_OK;
+}
+
 int launch_inputs(snn_network *net, InputsPart part = INPUTS_ALL)
 {
     if (net->n_loc == 0 || net->n_tot == 0) return SNN_OK;
@@ -108,165 +211,26 @@ int launch_inputs(snn_network *net, InputsPart part = INPUTS_ALL)
     a.nt_flags = net->na.nt_flags; a.n_pad = net->n_pad;
     a.part_i = net->part_i; a.part_t = net->part_t; a.n_chunks = net->n_chunks;
     for (int k = 0; k < K_TYPES; ++k) a.live_type[k] = net->live_type[k];
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (net->profile) {
-        if (net->ev_used == net->ev_pool.size()) {
-            hipEvent_t x, y;
-            HIP_TRY(hipEventCreate(&x), SNN_ERR_QUEUE);
-            HIP_TRY(hipEventCreate(&y), SNN_ERR_QUEUE);
-            net->ev_pool.emplace_back(x, y);
-        }
-        e0 = net->ev_pool[net->ev_used].first;
-        e1 = net->ev_pool[net->ev_used].second;
-        net->ev_counts.resize(net->ev_pool.size(), 1);
-        // LOCAL + REMOTE = one pass over W (counted on the REMOTE half; a lone shard has no REMOTE half)
-        net->ev_counts[net->ev_used] = (part == INPUTS_LOCAL && lc_count < net->n_chunks) ? 0 : 1;
-        ++net->ev_used;
-        HIP_TRY(hipEventRecord(e0, net->stream), SNN_ERR_QUEUE);
+    // LOCAL + REMOTE = one pass over W (counted on the REMOTE half; a lone shard has no REMOTE half)
+    hipEvent_t e1 = nullptr;
+    TRY(profile_open(net, PROFILE_GRAPH_PASS, (part == INPUTS_LOCAL && lc_count < net->n_chunks) ? 0 : 1, &e1));
+    if (net->csr && net->csr_ptr) {
+        CsrInputsArgs ca{};
+        ca.g = csr_graph(net);
+        ca.in = a;
+        const dim3 g((((net->n_loc + 63) / 64) * 64 + 255) / 256);
+        for_synapses(net->electrical, net->chemical, [&](auto E, auto C) {
+            hipLaunchKernelGGL((k_inputs_csr<E(), C()>), g, dim3(256), 0, net->stream, ca);
+        });
+    } else if (net->csr) {   // no graph set: no edges
+        HIP_TRY(hipMemsetAsync(net->part_i, 0, (size_t)net->ld * 4, net->stream), SNN_ERR_BUFFER_WRITE);
+        HIP_TRY(hipMemsetAsync(net->part_t, 0, (size_t)K_TYPES * net->ld * 4, net->stream), SNN_ERR_BUFFER_WRITE);
+    } else {
+        TRY(launch_inputs_dense(net, part, a, grid_chunks));
     }
-    if (net->csr) {
-        if (net->csr_ptr) {
-            CsrInputsArgs ca{};
-            ca.g = csr_graph(net);
-            ca.in = a;
-            dim3 g((((net->n_loc + 63) / 64) * 64 + 255) / 256);
-            if (net->electrical && net->chemical) hipLaunchKernelGGL((k_inputs_csr<true, true>), g, dim3(256), 0, net->stream, ca);
-            else if (net->electrical) hipLaunchKernelGGL((k_inputs_csr<true, false>), g, dim3(256), 0, net->stream, ca);
-            else hipLaunchKernelGGL((k_inputs_csr<false, true>), g, dim3(256), 0, net->stream, ca);
-        } else {   // no graph set: no edges
-            HIP_TRY(hipMemsetAsync(net->part_i, 0, (size_t)net->ld * 4, net->stream), SNN_ERR_BUFFER_WRITE);
-            HIP_TRY(hipMemsetAsync(net->part_t, 0, (size_t)K_TYPES * net->ld * 4, net->stream), SNN_ERR_BUFFER_WRITE);
-        }
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        if (net->profile) HIP_TRY(hipEventRecord(e1, net->stream), SNN_ERR_QUEUE);
-        return SNN_OK;
-    }
-    // shape of the pass: cache-resident matrices take the latency-oriented one-wave shape; streamed matrices the
-    // 4-columns-per-lane shape, or the 2-column shape while that would leave the chip under-filled
-    const bool resident = (size_t)net->n_tot * net->ld * 4 <= ((size_t)64 << 20);
-    const uint64_t waves4 = (uint64_t)((net->n_loc + 255) / 256) * grid_chunks;
-    // same-box A/B of the two streamed shapes (profiles/ab_input_shape.py, profiles/r03/ab_input_shape_by_size.txt): the
-    // 2-column shape wins by 0.8 - 2.4 % from 96x96 to 240x240 (waves4 up to 50 625), the 4-column shape by 0.5 % at 256x256
-    int shape = resident ? 0 : (waves4 < 57600 ? 2 : 1);
-    if (net->force_shape > 0 && !resident) shape = net->force_shape;     // SNN_AMD_INPUT_SHAPE=1|2 (experiments)
-    if (net->rstdp_pending && part != INPUTS_ALL) TRY(flush_rstdp(net));
-    const bool stdp_fused = net->stdp_pending && !net->rstdp_pending && part == INPUTS_ALL && shape != 0;
-    if (net->stdp_pending && !stdp_fused) TRY(flush_stdp(net));
-#if !SNN_HAVE_CUSTOM_MODEL
-    if (stdp_fused) {
-        // the STDP update of the previous step rides on this pass over W
-        net->stdp_pending = false;
-        const bool rows_only = net->stdp_pending_rows_only;
-        net->stdp_pending_rows_only = false;
-        a.W_rw = net->W; a.stdp_count = net->spike_count; a.stdp_flag = net->stdp_flag;
-        a.stdp_dcol = net->stdp_dcol; a.stdp_drow = net->stdp_drow; a.lattice_slot = net->lattice_slot;
-        a.dcol_stride = net->dcol_stride; a.n_lattices = (uint32_t)net->lattices.size();
-        a.stdp_rowbits = net->stdp_rowbits;
-#define SNN_LAUNCH_SSHAPE(E, C, SH)                                                                       \
-    do {                                                                                                 \
-        const dim3 g_((net->n_loc + InputsShape<SH>::TILE - 1) / InputsShape<SH>::TILE, grid_chunks);    \
-        if (rows_only) hipLaunchKernelGGL((k_inputs_dense<E, C, SH, K_TYPES, 2>), g_, dim3(InputsShape<SH>::THREADS), 0, net->stream, a); \
-        else hipLaunchKernelGGL((k_inputs_dense<E, C, SH, K_TYPES, 1>), g_, dim3(InputsShape<SH>::THREADS), 0, net->stream, a); \
-    } while (0)
-#define SNN_LAUNCH_SINPUTS(E, C)                                                                         \
-    do {                                                                                                 \
-        if (shape == 1) SNN_LAUNCH_SSHAPE(E, C, 1);                                                      \
-        else SNN_LAUNCH_SSHAPE(E, C, 2);                                                                 \
-    } while (0)
-        for (int k = 0; k < K_TYPES; ++k) a.live_type[k] = (uint32_t)k;     // the generic three-slot chemical variant
-        if (net->electrical && net->chemical) SNN_LAUNCH_SINPUTS(true, true);
-        else if (net->electrical) SNN_LAUNCH_SINPUTS(true, false);
-        else SNN_LAUNCH_SINPUTS(false, true);
-#undef SNN_LAUNCH_SINPUTS
-#undef SNN_LAUNCH_SSHAPE
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        if (net->profile) HIP_TRY(hipEventRecord(e1, net->stream), SNN_ERR_QUEUE);
-        return SNN_OK;
-    }
-#endif
-    if (net->rstdp_pending) {
-        // the reward-modulated weight update of the previous step rides on this pass over W
-        net->rstdp_pending = false;
-        RstdpInputsArgs ra{};
-        ra.in = a; ra.W = net->W; ra.C = net->trace;
-        ra.last_firing_time = net->na.last_firing_time; ra.lattice_slot = net->lattice_slot;
-        ra.rm = net->rm_dev; ra.rm_on = net->rm_on_dev;
-        ra.dop = net->reward_since_defer ? RM_DOPAMINE_BEFORE : RM_DOPAMINE;
-#define SNN_LAUNCH_RSHAPE(E, C, SH)                                                                       \
-    hipLaunchKernelGGL((k_inputs_rstdp<E, C, SH>),                                                       \
-                       dim3((net->n_loc + InputsShape<SH>::TILE - 1) / InputsShape<SH>::TILE, grid_chunks), \
-                       dim3(InputsShape<SH>::THREADS), 0, net->stream, ra)
-#define SNN_LAUNCH_RINPUTS(E, C)                                                                         \
-    do {                                                                                                 \
-        if (shape == 1) SNN_LAUNCH_RSHAPE(E, C, 1);                                                      \
-        else if (shape == 2) SNN_LAUNCH_RSHAPE(E, C, 2);                                                 \
-        else SNN_LAUNCH_RSHAPE(E, C, 0);                                                                 \
-    } while (0)
-        if (net->electrical && net->chemical) SNN_LAUNCH_RINPUTS(true, true);
-        else if (net->electrical) SNN_LAUNCH_RINPUTS(true, false);
-        else SNN_LAUNCH_RINPUTS(false, true);
-#undef SNN_LAUNCH_RINPUTS
-#undef SNN_LAUNCH_RSHAPE
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        if (net->profile) HIP_TRY(hipEventRecord(e1, net->stream), SNN_ERR_QUEUE);
-        return SNN_OK;
-    }
-#define SNN_LAUNCH_SHAPE(E, C, SH, NT)                                                                    \
-    hipLaunchKernelGGL((k_inputs_dense<E, C, SH, NT>),                                                   \
-                       dim3((net->n_loc + InputsShape<SH>::TILE - 1) / InputsShape<SH>::TILE, grid_chunks), \
-                       dim3(InputsShape<SH>::THREADS), 0, net->stream, a)
-#define SNN_LAUNCH_INPUTS(E, C, NT)                                                                      \
-    do {                                                                                                 \
-        if (shape == 1) SNN_LAUNCH_SHAPE(E, C, 1, NT);                                                   \
-        else if (shape == 2) SNN_LAUNCH_SHAPE(E, C, 2, NT);                                              \
-        else SNN_LAUNCH_SHAPE(E, C, 0, NT);                                                              \
-    } while (0)
-#if !SNN_HAVE_CUSTOM_MODEL
-#define SNN_LAUNCH_CHEM(E)                                                                               \
-    do {                                                                                                 \
-        if (net->n_live == 1) SNN_LAUNCH_INPUTS(E, true, 1);                                             \
-        else if (net->n_live == 2) SNN_LAUNCH_INPUTS(E, true, 2);                                        \
-        else SNN_LAUNCH_INPUTS(E, true, 3);                                                              \
-    } while (0)
-#else       // a library carrying generated code: the generic three-slot variant only (shorter compile)
-#define SNN_LAUNCH_CHEM(E)                                                                               \
-    do {                                                                                                 \
-        for (int k = 0; k < K_TYPES; ++k) a.live_type[k] = (uint32_t)k;                                  \
-        SNN_LAUNCH_INPUTS(E, true, 3);                                                                   \
-    } while (0)
-#endif
-    if (net->electrical && net->chemical) SNN_LAUNCH_CHEM(true);
-    else if (net->electrical) SNN_LAUNCH_INPUTS(true, false, 3);
-    else SNN_LAUNCH_CHEM(false);
-#undef SNN_LAUNCH_CHEM
-#undef SNN_LAUNCH_INPUTS
-#undef SNN_LAUNCH_SHAPE
     HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-    if (net->profile) HIP_TRY(hipEventRecord(e1, net->stream), SNN_ERR_QUEUE);
-    return SNN_OK;
+    return profile_close(net, e1);
 }
-
-// -DSNN_LAB_BUILD: a library for kernel experiments (profiles/experiments/README.md) that instantiates the model-templated kernels
-// for Izhikevich and Hodgkin-Huxley only -- a quarter of the compile time; never the library the tests or the bench load by default
-#ifdef SNN_LAB_BUILD
-#define SNN_FOR_MODEL(MACRO)                                                                                         \
-    switch (net->model) {                                                                                            \
-    case 2: MACRO(2); break;                                                                                         \
-    default: MACRO(0); break;                                                                                        \
-    }
-#else
-#define SNN_FOR_MODEL(MACRO)                                                                                         \
-    switch (net->model) {                                                                                            \
-    case 1: MACRO(1); break;                                                                                         \
-    case 2: MACRO(2); break;                                                                                         \
-    case 3: MACRO(3); break;                                                                                         \
-    case 4: MACRO(4); break;                                                                                         \
-    case 5: MACRO(5); break;                                                                                         \
-    case 6: MACRO(6); break;                                                                                         \
-    case 7: MACRO(7); break;                                                                                         \
-    default: MACRO(0); break;                                                                                        \
-    }
-#endif
 
 int launch_update(snn_network *net)
 {
@@ -321,26 +285,12 @@ int launch_update(snn_network *net)
         for (int k = 0; k < K_TYPES; ++k) if (a.live_mask >> k & 1u) touch.by_column[touch.n_column++] = net->tcount + (size_t)k * net->ld;
         if (net->update_all_planes == 3) touch.n_neuron = touch.n_column = 0;      // (A/B: the wide form without the cache warming)
     }
-#define SNN_LAUNCH_UPDATE(M) do { \
-        if (wide) hipLaunchKernelGGL((k_update_wide<M>), grid, dim3(256), 0, net->stream, a, touch); \
-        else if (all_planes) hipLaunchKernelGGL((k_update<M, true>), grid, dim3(ub), 0, net->stream, a); \
-        else hipLaunchKernelGGL((k_update<M, false>), grid, dim3(ub), 0, net->stream, a); } while (0)
-    switch (net->model) {
-    case SNN_MODEL_HODGKIN_HUXLEY: SNN_LAUNCH_UPDATE(2); break;
-#ifndef SNN_LAB_BUILD
-    case SNN_MODEL_LIF: SNN_LAUNCH_UPDATE(1); break;
-    case SNN_MODEL_QUADRATIC_INTEGRATE_AND_FIRE: SNN_LAUNCH_UPDATE(3); break;
-    case SNN_MODEL_SIMPLE_LIF: SNN_LAUNCH_UPDATE(4); break;
-    case SNN_MODEL_ADAPTIVE_LIF: SNN_LAUNCH_UPDATE(5); break;
-    case SNN_MODEL_ADAPTIVE_EXP_LIF: SNN_LAUNCH_UPDATE(6); break;
-    case SNN_MODEL_LEAKY_IZHIKEVICH: SNN_LAUNCH_UPDATE(7); break;
-#endif
-#if SNN_HAVE_CUSTOM_NEURON
-    case SNN_MODEL_CUSTOM: hipLaunchKernelGGL((k_update<CUSTOM_MODEL, false>), grid, dim3(ub), 0, net->stream, a); break;
-#endif
-    default: SNN_LAUNCH_UPDATE(0); break;
-    }
-#undef SNN_LAUNCH_UPDATE
+    for_model(UpdateModels{}, net->model, [&](auto M) {
+        if constexpr (M() == CUSTOM_MODEL) hipLaunchKernelGGL((k_update<M(), false>), grid, dim3(ub), 0, net->stream, a);
+        else if (wide) hipLaunchKernelGGL((k_update_wide<M()>), grid, dim3(256), 0, net->stream, a, touch);
+        else if (all_planes) hipLaunchKernelGGL((k_update<M(), true>), grid, dim3(ub), 0, net->stream, a);
+        else hipLaunchKernelGGL((k_update<M(), false>), grid, dim3(ub), 0, net->stream, a);
+    });
     HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
     return SNN_OK;
 }
@@ -351,18 +301,10 @@ int launch_plasticity_kernels(snn_network *net);
 int launch_plasticity(snn_network *net)
 {
     if (!net->any_plasticity || net->nn == 0) return SNN_OK;
-    if (!net->profile) return launch_plasticity_kernels(net);
-    if (net->ev_used_pl == net->ev_pool_pl.size()) {
-        hipEvent_t x, y;
-        HIP_TRY(hipEventCreate(&x), SNN_ERR_QUEUE);
-        HIP_TRY(hipEventCreate(&y), SNN_ERR_QUEUE);
-        net->ev_pool_pl.emplace_back(x, y);
-    }
-    const auto ev = net->ev_pool_pl[net->ev_used_pl++];
-    HIP_TRY(hipEventRecord(ev.first, net->stream), SNN_ERR_QUEUE);
+    hipEvent_t e1 = nullptr;
+    TRY(profile_open(net, PROFILE_PLASTICITY, 1, &e1));
     TRY(launch_plasticity_kernels(net));
-    HIP_TRY(hipEventRecord(ev.second, net->stream), SNN_ERR_QUEUE);
-    return SNN_OK;
+    return profile_close(net, e1);
 }
 
 // small dense unsharded networks under STDP (no BCM lattice among the plastic ones): compaction and both scatters in one launch
@@ -703,55 +645,24 @@ int fused_step_args(snn_network *net, InputsArgs &a, UpdateArgs &u, bool in_plac
     return SNN_OK;
 }
 
-// HIP events around the launch that streams the graph (snn_profile_*)
-int profile_open(snn_network *net, hipEvent_t *e1)
-{
-    *e1 = nullptr;
-    if (!net->profile) return SNN_OK;
-    if (net->ev_used == net->ev_pool.size()) {
-        hipEvent_t x, y;
-        HIP_TRY(hipEventCreate(&x), SNN_ERR_QUEUE);
-        HIP_TRY(hipEventCreate(&y), SNN_ERR_QUEUE);
-        net->ev_pool.emplace_back(x, y);
-    }
-    hipEvent_t e0 = net->ev_pool[net->ev_used].first;
-    *e1 = net->ev_pool[net->ev_used].second;
-    net->ev_counts.resize(net->ev_pool.size(), 1);
-    net->ev_counts[net->ev_used] = 1;
-    ++net->ev_used;
-    HIP_TRY(hipEventRecord(e0, net->stream), SNN_ERR_QUEUE);
-    return SNN_OK;
-}
-
 int launch_step_resident(snn_network *net)
 {
     ResidentArgs r{};
     TRY(fused_step_args(net, r.in, r.up));
     hipEvent_t e1 = nullptr;
-    TRY(profile_open(net, &e1));
+    TRY(profile_open(net, PROFILE_GRAPH_PASS, 1, &e1));
     // a chunk's rows over four wavefronts (k_step_resident_q) where the workgroup stays within 512 threads: at most two chunks
     // (a network of at most 64 rows has one quarter's worth of them: nothing to spread, and the turns cost 1 - 8 us)
     const bool quarters = net->resident_quarters && net->n_chunks <= 2 && net->n_tot > 64;
     const dim3 grid((net->n_loc + 63) / 64), block(64 * net->n_chunks * (quarters ? 4 : 1));
-#define SNN_RESIDENT(M)                                                                                              \
-    do {                                                                                                             \
-        if (quarters && net->electrical && net->chemical) hipLaunchKernelGGL((k_step_resident_q<M, true, true>), grid, block, 0, net->stream, r); \
-        else if (quarters && net->electrical) hipLaunchKernelGGL((k_step_resident_q<M, true, false>), grid, block, 0, net->stream, r);            \
-        else if (quarters) hipLaunchKernelGGL((k_step_resident_q<M, false, true>), grid, block, 0, net->stream, r);                              \
-        else if (net->electrical && net->chemical) hipLaunchKernelGGL((k_step_resident<M, true, true>), grid, block, 0, net->stream, r);  \
-        else if (net->electrical) hipLaunchKernelGGL((k_step_resident<M, true, false>), grid, block, 0, net->stream, r);             \
-        else hipLaunchKernelGGL((k_step_resident<M, false, true>), grid, block, 0, net->stream, r);                                  \
-    } while (0)
-#if !SNN_HAVE_CUSTOM_MODEL        // a library carrying a generated model has the one-launch step for that model only (shorter compile)
-    SNN_FOR_MODEL(SNN_RESIDENT)
-#elif SNN_HAVE_CUSTOM_NEURON
-    SNN_RESIDENT(CUSTOM_MODEL);
-#else
-    (void)grid, (void)block;
-#endif
-#undef SNN_RESIDENT
+    for_model(ResidentStepModels{}, net->model, [&](auto M) {
+        for_synapses(net->electrical, net->chemical, [&](auto E, auto C) {
+            if (quarters) hipLaunchKernelGGL((k_step_resident_q<M(), E(), C()>), grid, block, 0, net->stream, r);
+            else hipLaunchKernelGGL((k_step_resident<M(), E(), C()>), grid, block, 0, net->stream, r);
+        });
+    });
     HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-    if (e1) HIP_TRY(hipEventRecord(e1, net->stream), SNN_ERR_QUEUE);
+    TRY(profile_close(net, e1));
     net->shadow_cur ^= 1;
     return SNN_OK;
 }
@@ -785,28 +696,17 @@ int launch_dense_close(snn_network *net)
     const bool one_type = net->chemical && net->n_live == 1;
     if (one_type) for (int k = 0; k < K_TYPES; ++k) r.in.live_type[k] = net->live_type[k];
     hipEvent_t e1 = nullptr;
-    TRY(profile_open(net, &e1));
+    TRY(profile_open(net, PROFILE_GRAPH_PASS, 1, &e1));
     const dim3 grid(tiles, net->n_chunks), block(256);
-#define SNN_DENSE_CLOSE_SHAPE(M, SH)                                                                                                  \
-    do {                                                                                                                              \
-        if (!net->chemical) hipLaunchKernelGGL((k_inputs_dense_close<M, true, false, SH, 3>), grid, block, 0, net->stream, r);        \
-        else if (one_type) hipLaunchKernelGGL((k_inputs_dense_close<M, true, true, SH, 1>), grid, block, 0, net->stream, r);          \
-        else hipLaunchKernelGGL((k_inputs_dense_close<M, true, true, SH, 3>), grid, block, 0, net->stream, r);                        \
-    } while (0)
-#define SNN_DENSE_CLOSE(M)                                                                                                            \
-    do {                                                                                                                              \
-        if (shape == 1) SNN_DENSE_CLOSE_SHAPE(M, 1);                                                                                  \
-        else SNN_DENSE_CLOSE_SHAPE(M, 2);                                                                                             \
-    } while (0)
-#if !SNN_HAVE_CUSTOM_MODEL
-    SNN_FOR_MODEL(SNN_DENSE_CLOSE)
-#else
-    (void)grid, (void)block;
-#endif
-#undef SNN_DENSE_CLOSE
-#undef SNN_DENSE_CLOSE_SHAPE
+    for_model(FusedModels{}, net->model, [&](auto M) {
+        for_value<1, 2>(shape, [&](auto SH) {
+            if (!net->chemical) hipLaunchKernelGGL((k_inputs_dense_close<M(), true, false, SH(), 3>), grid, block, 0, net->stream, r);
+            else if (one_type) hipLaunchKernelGGL((k_inputs_dense_close<M(), true, true, SH(), 1>), grid, block, 0, net->stream, r);
+            else hipLaunchKernelGGL((k_inputs_dense_close<M(), true, true, SH(), 3>), grid, block, 0, net->stream, r);
+        });
+    });
     HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-    if (e1) HIP_TRY(hipEventRecord(e1, net->stream), SNN_ERR_QUEUE);
+    TRY(profile_close(net, e1));
     net->shadow_cur ^= 1;
     return SNN_OK;
 }
@@ -900,6 +800,17 @@ int run_snapshot(snn_network *net, bool restore)
     return SNN_OK;
 }
 
+// The forms of k_run_resident <MODEL, REGISTERS, CELLS, CHEM, STDP, LEND>, and the models with a REGISTERS variant of each: the
+// kernel carries their update itself
+enum RunForm { RUN_PLAIN, RUN_CELLS, RUN_CHEM, RUN_CHEM_CELLS, RUN_CHEM_LEND, RUN_STDP };
+constexpr bool run_form_in_registers(int model, int form)
+{
+    if (form == RUN_PLAIN || form == RUN_CELLS)
+        return model == SNN_MODEL_IZHIKEVICH || model == SNN_MODEL_LIF || model == SNN_MODEL_QUADRATIC_INTEGRATE_AND_FIRE ||
+               model == SNN_MODEL_SIMPLE_LIF;
+    return form != RUN_CHEM_CELLS && model == SNN_MODEL_IZHIKEVICH;
+}
+
 int launch_run_resident(snn_network *net, uint64_t iterations, uint64_t steps_before = 0)
 {
     if (!net->run_granules) {
@@ -978,65 +889,30 @@ int launch_run_resident(snn_network *net, uint64_t iterations, uint64_t steps_be
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
         // profiling: one event pair around the launch, counted as `steps` passes over the graph
         hipEvent_t e1 = nullptr;
-        TRY(profile_open(net, &e1));
-        if (e1) net->ev_counts[net->ev_used - 1] = (int)steps;
+        TRY(profile_open(net, PROFILE_GRAPH_PASS, (int)steps, &e1));
         const dim3 grid(n_groups), block(1024);
-#define SNN_RUN_RESIDENT(M) hipLaunchKernelGGL((k_run_resident<M, false, false>), grid, block, 0, net->stream, r)
-#define SNN_RUN_RESIDENT_CELLS(M) hipLaunchKernelGGL((k_run_resident<M, false, true>), grid, block, 0, net->stream, r)
-#define SNN_RUN_RESIDENT_CHEM(M) hipLaunchKernelGGL((k_run_resident<M, false, false, true>), grid, block, 0, net->stream, r)
-#define SNN_RUN_RESIDENT_CHEM_CELLS(M) hipLaunchKernelGGL((k_run_resident<M, false, true, true>), grid, block, 0, net->stream, r)
-#define SNN_RUN_RESIDENT_CHEM_LEND(M) hipLaunchKernelGGL((k_run_resident<M, false, false, true, false, true>), grid, block, 0, net->stream, r)
-#define SNN_RUN_RESIDENT_STDP(M) hipLaunchKernelGGL((k_run_resident<M, false, false, false, true>), grid, block, 0, net->stream, r)
-#if !SNN_HAVE_CUSTOM_MODEL
-        // neuron state in registers for the whole run where the kernel carries the model's update itself
-        const bool regs = !r.up.has_nt && !r.up.bcm && !net->chemical;
-        if (stdp && regs && net->model == SNN_MODEL_IZHIKEVICH) {                  // weight updates inside the run
-            hipLaunchKernelGGL((k_run_resident<0, true, false, false, true>), grid, block, 0, net->stream, r);
-        } else if (stdp) {
-            SNN_FOR_MODEL(SNN_RUN_RESIDENT_STDP);
-        } else if (net->chemical && net->nc) {                                     // chemical synapses: the generic update
-            SNN_FOR_MODEL(SNN_RUN_RESIDENT_CHEM_CELLS);
-        } else if (net->chemical && net->electrical && net->n_tot <= CHUNK && net->model == SNN_MODEL_IZHIKEVICH) {
-            // (one chunk at most, both kinds of synapse: the idle wavefronts take the transmitter chains)
-            hipLaunchKernelGGL((k_run_resident<0, true, false, true, false, true>), grid, block, 0, net->stream, r);
-        } else if (net->chemical && net->electrical && net->n_tot <= CHUNK) {
-            SNN_FOR_MODEL(SNN_RUN_RESIDENT_CHEM_LEND);
-        } else if (net->chemical && net->model == SNN_MODEL_IZHIKEVICH) {          // ... Izhikevich: receptors and transmitters resident too
-            hipLaunchKernelGGL((k_run_resident<0, true, false, true>), grid, block, 0, net->stream, r);
-        } else if (net->chemical) {
-            SNN_FOR_MODEL(SNN_RUN_RESIDENT_CHEM);
-        } else if (net->nc && regs && net->model == SNN_MODEL_IZHIKEVICH) {        // rows that are spike-train cells
-            hipLaunchKernelGGL((k_run_resident<0, true, true>), grid, block, 0, net->stream, r);
-        } else if (net->nc && regs && net->model == SNN_MODEL_LIF) {
-            hipLaunchKernelGGL((k_run_resident<1, true, true>), grid, block, 0, net->stream, r);
-        } else if (net->nc && regs && net->model == SNN_MODEL_QUADRATIC_INTEGRATE_AND_FIRE) {
-            hipLaunchKernelGGL((k_run_resident<3, true, true>), grid, block, 0, net->stream, r);
-        } else if (net->nc && regs && net->model == SNN_MODEL_SIMPLE_LIF) {
-            hipLaunchKernelGGL((k_run_resident<4, true, true>), grid, block, 0, net->stream, r);
-        } else if (net->nc) {
-            SNN_FOR_MODEL(SNN_RUN_RESIDENT_CELLS);
-        } else if (regs && net->model == SNN_MODEL_IZHIKEVICH) {
-            hipLaunchKernelGGL((k_run_resident<0, true, false>), grid, block, 0, net->stream, r);
-        } else if (regs && net->model == SNN_MODEL_LIF) {
-            hipLaunchKernelGGL((k_run_resident<1, true, false>), grid, block, 0, net->stream, r);
-        } else if (regs && net->model == SNN_MODEL_QUADRATIC_INTEGRATE_AND_FIRE) {
-            hipLaunchKernelGGL((k_run_resident<3, true, false>), grid, block, 0, net->stream, r);
-        } else if (regs && net->model == SNN_MODEL_SIMPLE_LIF) {
-            hipLaunchKernelGGL((k_run_resident<4, true, false>), grid, block, 0, net->stream, r);
-        } else {
-            SNN_FOR_MODEL(SNN_RUN_RESIDENT);
-        }
-#else
-        (void)grid, (void)block;
-#endif
-#undef SNN_RUN_RESIDENT
-#undef SNN_RUN_RESIDENT_CELLS
-#undef SNN_RUN_RESIDENT_CHEM
-#undef SNN_RUN_RESIDENT_CHEM_CELLS
-#undef SNN_RUN_RESIDENT_STDP
-#undef SNN_RUN_RESIDENT_CHEM_LEND
+        // the form of the run: weight updates inside it | chemical synapses: the generic update, with rows that are spike-train
+        // cells, or (one chunk at most, both kinds of synapse) the idle wavefronts taking the transmitter chains | electrical only
+        const bool cells = net->nc != 0, chem = net->chemical && !stdp;
+        const int form = stdp ? RUN_STDP : chem && cells ? RUN_CHEM_CELLS : chem && net->electrical && net->n_tot <= CHUNK ? RUN_CHEM_LEND
+                       : chem ? RUN_CHEM : cells ? RUN_CELLS : RUN_PLAIN;
+        // ... and whether the neuron state stays in registers for the whole run (the chemical forms: receptors and transmitters too)
+        const bool registers = run_form_in_registers(net->model, form) && (chem || (!r.up.has_nt && !r.up.bcm && !net->chemical));
+        for_value<RUN_CELLS, RUN_CHEM, RUN_CHEM_CELLS, RUN_CHEM_LEND, RUN_STDP, RUN_PLAIN>(form, [&](auto F) {
+            constexpr bool CELLS = F() == RUN_CELLS || F() == RUN_CHEM_CELLS, LEND = F() == RUN_CHEM_LEND, STDP = F() == RUN_STDP;
+            constexpr bool CHEM = F() == RUN_CHEM || F() == RUN_CHEM_CELLS || LEND;
+            auto run = [&](auto M, auto REGISTERS) {
+                hipLaunchKernelGGL((k_run_resident<M(), REGISTERS(), CELLS, CHEM, STDP, LEND>), grid, block, 0, net->stream, r);
+            };
+            if (registers)
+                for_model(RunRegisterModels{}, net->model, [&](auto M) {
+                    if constexpr (run_form_in_registers(M(), F())) run(M, bool_c<true>{});
+                });
+            else
+                for_model(FusedModels{}, net->model, [&](auto M) { run(M, bool_c<false>{}); });
+        });
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        if (e1) HIP_TRY(hipEventRecord(e1, net->stream), SNN_ERR_QUEUE);
+        TRY(profile_close(net, e1));
         if (net->run_timing) {          // debugging aid: workgroup 0's phases in shader clocks per step
             hvec<unsigned long long> t((size_t)grid.x * 4);
             HIP_TRY(hipMemcpyAsync(t.data(), net->run_timing, t.size() * 8, hipMemcpyDeviceToHost, net->stream), SNN_ERR_BUFFER_READ);
@@ -1208,28 +1084,22 @@ int launch_step_csr(snn_network *net, CsrStepPart part = CSR_STEP_ALL, bool pack
     }
     hipEvent_t e1 = nullptr;
     if (waves || tail_blocks) {
-        TRY(profile_open(net, &e1));
-        if (e1 && part == CSR_STEP_BORDER && net->n_interior) net->ev_counts[net->ev_used - 1] = 0;   // the interior launch counts the pass
+        TRY(profile_open(net, PROFILE_GRAPH_PASS, (part == CSR_STEP_BORDER && net->n_interior) ? 0 : 1, &e1));   // (the interior launch counts the pass)
         const dim3 grid((waves + 3) / 4 + tail_blocks), block(256);
-#define SNN_CSR_STEP(M)                                                                                              \
-    do {                                                                                                             \
-        if (image && c.pack.ptr) hipLaunchKernelGGL((k_step_csr_img<M, true>), grid, block, 0, net->stream, c);              \
-        else if (image) hipLaunchKernelGGL((k_step_csr_img<M, false>), grid, block, 0, net->stream, c);                        \
-        else if (net->peer_run && net->electrical && net->chemical) hipLaunchKernelGGL((k_step_csr<M, true, true, true>), grid, block, 0, net->stream, c); \
-        else if (net->peer_run && net->electrical) hipLaunchKernelGGL((k_step_csr<M, true, false, true>), grid, block, 0, net->stream, c); \
-        else if (net->peer_run) hipLaunchKernelGGL((k_step_csr<M, false, true, true>), grid, block, 0, net->stream, c);        \
-        else if (net->electrical && net->chemical) hipLaunchKernelGGL((k_step_csr<M, true, true>), grid, block, 0, net->stream, c);  \
-        else if (net->electrical) hipLaunchKernelGGL((k_step_csr<M, true, false>), grid, block, 0, net->stream, c);             \
-        else hipLaunchKernelGGL((k_step_csr<M, false, true>), grid, block, 0, net->stream, c);                                  \
-    } while (0)
-#if !SNN_HAVE_CUSTOM_MODEL
-        SNN_FOR_MODEL(SNN_CSR_STEP)
-#else
-        (void)grid, (void)block;
-#endif
-#undef SNN_CSR_STEP
+        for_model(FusedModels{}, net->model, [&](auto M) {
+            if (image)
+                for_bool(c.pack.ptr != nullptr, [&](auto PACK) {
+                    hipLaunchKernelGGL((k_step_csr_img<M(), PACK()>), grid, block, 0, net->stream, c);
+                });
+            else
+                for_synapses(net->electrical, net->chemical, [&](auto E, auto C) {
+                    for_bool(net->peer_run, [&](auto PEER) {
+                        hipLaunchKernelGGL((k_step_csr<M(), E(), C(), PEER()>), grid, block, 0, net->stream, c);
+                    });
+                });
+        });
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        if (e1) HIP_TRY(hipEventRecord(e1, net->stream), SNN_ERR_QUEUE);
+        TRY(profile_close(net, e1));
     }
     if (part != CSR_STEP_BORDER) net->shadow_cur ^= 1;       // S(t+1) is complete once the last part is enqueued
     return SNN_OK;
