@@ -501,8 +501,16 @@ int snn_get_average_voltage_history(snn_network_t *net, uint32_t id, float *dst,
 int snn_get_eeg_history(snn_network_t *net, uint32_t id, float *dst, size_t steps);
 int snn_get_spike_counts(snn_network_t *net, uint32_t id, uint32_t *dst, size_t count);
 
-/* Tuning switches (results never depend on them; defaults in brackets, also settable through the environment when the
- * handle is created: SNN_AMD_<NAME in upper case>): "fused_step" [1] one-launch step for small lattices and for
+/* Tuning switches (results never depend on them; defaults in brackets).  Read from the environment as well, as
+ * SNN_AMD_<NAME in upper case> when the handle is created: "fused_step", "dense_close", "resident_quarters", "cells_in_step",
+ * "update_packs", "update_all_planes", "csr_xcd_bands", "csr_image", "halo_direct", "halo_peer", "defer_rstdp", "defer_stdp",
+ * "uniform_params", "persistent_run", "persistent_chem", "persistent_stdp", "input_shape", "pinned_copies", "stdp_small",
+ * "stdp_columns_form" and "verify" -- of such a variable only the first character counts (a digit; anything else switches
+ * an on / off switch on and gives the others the value an out-of-range option gives).  Options only, without a variable:
+ * "halo_peer_delay", "halo_peer_spin_limit", "run_resident_spin_limit", "run_resident_fault_step",
+ * "run_resident_chunk_steps", "run_timing", "verify_fault".  A variable only, without an option:
+ * SNN_AMD_DENSE_CLOSE_MAX_CHUNKS=n ("dense_close" only up to n chunks of presynaptic rows; experiments).
+ * "fused_step" [1] one-launch step for small lattices and for
  * sparse handles; "dense_close" [0] 1: streamed dense matrices on unsharded handles with gap junctions: the last workgroup of a column
  * tile of the input pass updates the tile's neurons in the same launch (k_inputs_dense_close; measured slower than input pass +
  * k_update); "resident_quarters" [1] the one-launch step of small dense networks (at most 512 presynaptic rows) spreads a chunk's 256 rows

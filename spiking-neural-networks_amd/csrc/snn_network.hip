@@ -41,28 +41,8 @@ int snn_network_create(int device, int neuron_model, int nt_kinetics, int recept
     HIP_TRY(hipSetDevice(device), SNN_ERR_GET_DEVICE);
     snn_network *net = new snn_network();
     net->device = device;
-    if (const char *e = getenv("SNN_AMD_FUSED_STEP")) net->fused_step = (e[0] != '0');
-    if (const char *e = getenv("SNN_AMD_DENSE_CLOSE")) net->dense_close = (e[0] != '0');
-    if (const char *e = getenv("SNN_AMD_DENSE_CLOSE_MAX_CHUNKS")) net->dense_close_max_chunks = (uint32_t)strtoul(e, nullptr, 10);
-    if (const char *e = getenv("SNN_AMD_PINNED_COPIES")) net->pinned_copies = (e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1;
-    if (const char *e = getenv("SNN_AMD_CSR_XCD_BANDS")) net->csr_xcd_bands = (e[0] != '0');
-    if (const char *e = getenv("SNN_AMD_CSR_IMAGE")) net->csr_image = (e[0] != '0');
-    if (const char *e = getenv("SNN_AMD_RESIDENT_QUARTERS")) net->resident_quarters = (e[0] != '0');
-    if (const char *e = getenv("SNN_AMD_HALO_DIRECT")) net->halo_direct = (e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1;
-    if (const char *e = getenv("SNN_AMD_UPDATE_PACKS")) net->update_packs = (e[0] != '0');
-    if (const char *e = getenv("SNN_AMD_UPDATE_ALL_PLANES")) net->update_all_planes = (e[0] >= '0' && e[0] <= '3') ? e[0] - '0' : 1;
-    if (const char *e = getenv("SNN_AMD_CELLS_IN_STEP")) net->cells_in_step = (e[0] != '0');
-    if (const char *e = getenv("SNN_AMD_DEFER_RSTDP")) net->defer_rstdp = (e[0] != '0');
-    if (const char *e = getenv("SNN_AMD_DEFER_STDP")) net->defer_stdp = (e[0] >= '0' && e[0] <= '3') ? e[0] - '0' : 1;
-    if (const char *e = getenv("SNN_AMD_UNIFORM_PARAMS")) net->uniform_params = (e[0] != '0');
-    if (const char *e = getenv("SNN_AMD_PERSISTENT_RUN")) net->persistent_run = (e[0] != '0');
-    if (const char *e = getenv("SNN_AMD_PERSISTENT_CHEM")) net->persistent_chem = (e[0] != '0');
-    if (const char *e = getenv("SNN_AMD_PERSISTENT_STDP")) net->persistent_stdp = (e[0] != '0');
-    if (const char *e = getenv("SNN_AMD_HALO_PEER")) net->halo_peer = (e[0] != '0');
-    if (const char *e = getenv("SNN_AMD_STDP_COLUMNS_FORM")) net->stdp_columns_form = (e[0] == '1') ? 1 : 0;
-    if (const char *e = getenv("SNN_AMD_STDP_SMALL")) net->stdp_small = (e[0] != '0');
-    if (const char *e = getenv("SNN_AMD_VERIFY")) net->verify = (e[0] != '0');
-    if (const char *e = getenv("SNN_AMD_INPUT_SHAPE")) net->force_shape = (e[0] == '1') ? 1 : ((e[0] == '2') ? 2 : 0);
+    for (const OptionRow &r : OPTION_TABLE)
+        if (const char *e = r.source != OPTION_ONLY ? getenv(option_env_name(r).c_str()) : nullptr) net->opt.*r.member = option_from_env(r, e);
     net->model = neuron_model; net->nt_kind = nt_kinetics; net->rc_kind = receptor_kinetics;
     net->st_kind = spike_train_model;
     if (hipStreamCreateWithFlags(&net->own_stream, hipStreamNonBlocking) != hipSuccess) {
@@ -339,7 +319,7 @@ int snn_fill_graph_synthetic(snn_network_t *net, uint64_t seed, float lo, float 
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
         HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
     }
-    net->counts_dirty = true;
+    net->cache.counts_dirty = true;
     return SNN_OK;
 }
 ABI_CATCH
@@ -483,14 +463,14 @@ static int set_graph_csr_impl(snn_network_t *net, const uint64_t *row_ptr, const
     net->edge_slot_host.swap(edge_slot);
     if (net->sharded && net->n_shards > 1) { net->sell_pre_host.swap(sell_pre); net->slice_ptr_host.swap(slice_ptr); }
     else { net->sell_pre_host.clear(); net->slice_ptr_host.clear(); }
-    net->counts_dirty = true;
+    net->cache.counts_dirty = true;
     net->halo_need.swap(halo_need); net->halo_send.swap(halo_send);
     net->halo_committed = false; net->x_dirty = true;
     if (list_cells) {
         net->cell_list_host.swap(cells);
         net->cell_list_dev = std::move(cells_d);
         net->n_cells_listed = (uint32_t)net->cell_list_host.size();
-        net->view_dirty = true;
+        net->cache.view_dirty = true;
     }
     // a reward-modulated handle keeps modulating: zeroed traces for the new edges, sized by the committed graph (see above)
     if (net->any_modulation || net->any_conn_kind) TRY(ensure_traces(net));
@@ -926,7 +906,7 @@ int snn_set_history(snn_network_t *net, int voltage_history, int spike_history) 
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
     if ((voltage_history != 0) != (net->want_vhist != 0) || (spike_history != 0) != (net->want_raster != 0)) {
         // switching what is recorded restarts the record so that all rows cover the same steps
-        net->hist_steps = 0; net->hist_tick = 0;
+        net->cur.hist_steps = 0; net->cur.hist_tick = 0;
     }
     net->want_vhist = voltage_history ? 1 : 0;
     net->want_raster = spike_history ? 1 : 0;
@@ -937,7 +917,7 @@ ABI_CATCH
 int snn_reset_history(snn_network_t *net) ABI_TRY
 {
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
-    net->hist_steps = 0; net->hist_tick = 0;
+    net->cur.hist_steps = 0; net->cur.hist_tick = 0;
     if (net->finalized && net->spike_counts) {
         HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
         TRY(end_run(net));
@@ -991,7 +971,7 @@ int snn_set_graph_history(snn_network_t *net, uint32_t id, int enable) ABI_TRY
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
     TRY(end_run(net));
     if (enable < 0 || enable > 2) return fail(SNN_ERR_BAD_ARG, "enable: 0 off, 1 after the weight updates, 2 before them");
-    if ((enable != 0) != (net->want_whist[l->slot] != 0)) { net->hist_steps = 0; net->hist_tick = 0; }
+    if ((enable != 0) != (net->want_whist[l->slot] != 0)) { net->cur.hist_steps = 0; net->cur.hist_tick = 0; }
     net->want_whist[l->slot] = enable;
     net->any_whist = false;
     for (int v : net->want_whist) net->any_whist |= (v != 0);
@@ -1006,7 +986,7 @@ int snn_get_graph_history(snn_network_t *net, uint32_t id, float *dst, size_t st
     const LatticeInfo *l = find_lattice(net, id);
     if (!l || l->spike_train) return fail(SNN_ERR_BAD_ARG, "graph histories belong to neuron lattices");
     if (!net->want_whist[l->slot]) return fail(SNN_ERR_BAD_STATE, "graph history is off for this lattice");
-    if (steps != net->hist_steps) return fail(SNN_ERR_DIM_MISMATCH, "history size mismatch");
+    if (steps != net->cur.hist_steps) return fail(SNN_ERR_DIM_MISMATCH, "history size mismatch");
     if (steps == 0 || l->count == 0) return SNN_OK;
     if (!dst) return fail(SNN_ERR_BAD_ARG, "dst is null");
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
@@ -1020,7 +1000,7 @@ int snn_set_history_stride(snn_network_t *net, uint32_t every) ABI_TRY
 {
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
     if (every == 0) return fail(SNN_ERR_BAD_ARG, "stride must be at least 1");
-    if (every != net->hist_every) { net->hist_steps = 0; net->hist_tick = 0; }
+    if (every != net->hist_every) { net->cur.hist_steps = 0; net->cur.hist_tick = 0; }
     net->hist_every = every;
     return SNN_OK;
 }
@@ -1031,7 +1011,7 @@ int snn_set_reduced_history(snn_network_t *net, int average_voltage, int eeg, in
 {
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
     if ((average_voltage != 0) != (net->want_avg != 0) || (eeg != 0) != (net->want_eeg != 0))
-        net->hist_steps = 0, net->hist_tick = 0;      // all recorded rows must cover the same steps
+        net->cur.hist_steps = 0, net->cur.hist_tick = 0;      // all recorded rows must cover the same steps
     net->want_avg = average_voltage ? 1 : 0;
     net->want_eeg = eeg ? 1 : 0;
     net->want_counts = spike_counts ? 1 : 0;
@@ -1047,7 +1027,7 @@ static int get_summary(snn_network_t *net, uint32_t id, float *dst, size_t steps
     const LatticeInfo *l = find_lattice(net, id);
     if (!l || l->spike_train) return fail(SNN_ERR_BAD_ARG, "reduced histories exist for neuron lattices");
     if (!(eeg ? net->want_eeg : net->want_avg)) return fail(SNN_ERR_BAD_STATE, "this reduced history is off");
-    if (steps != net->hist_steps) return fail(SNN_ERR_DIM_MISMATCH, "history size mismatch");
+    if (steps != net->cur.hist_steps) return fail(SNN_ERR_DIM_MISMATCH, "history size mismatch");
     if (steps == 0) return SNN_OK;
     if (!dst) return fail(SNN_ERR_BAD_ARG, "dst is null");
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
@@ -1084,7 +1064,7 @@ ABI_CATCH
 int snn_get_clock(const snn_network_t *net, uint64_t *clock) ABI_TRY
 {
     if (!net || !clock) return fail(SNN_ERR_BAD_ARG, "null argument");
-    *clock = (uint64_t)net->clock;
+    *clock = (uint64_t)net->cur.clock;
     return SNN_OK;
 }
 ABI_CATCH
@@ -1095,8 +1075,8 @@ int snn_reset_timing(snn_network_t *net) ABI_TRY
     if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
     TRY(end_run(net));
-    net->clock = 0;
-    net->view_dirty = true;
+    net->cur.clock = 0;
+    net->cache.view_dirty = true;
     for (auto &c : net->st_clock) c = 0;
     HIP_TRY(hipMemsetAsync(net->na.last_firing_time, 0xFF, (size_t)net->n_pad * 4, net->stream), SNN_ERR_BUFFER_WRITE);
     HIP_TRY(hipMemsetAsync(net->ca.last_firing_time, 0xFF, (size_t)net->c_pad * 4, net->stream), SNN_ERR_BUFFER_WRITE);
@@ -1112,8 +1092,8 @@ int snn_set_clock(snn_network_t *net, uint64_t clock) ABI_TRY
     if (clock > 0x7FFFFFFFull) return fail(SNN_ERR_BAD_ARG, "the clock must fit the firing times' 31 bits");
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
     TRY(end_run(net));
-    net->clock = (long long)clock;
-    net->view_dirty = true;            // the cells' gap-junction values are functions of the clock
+    net->cur.clock = (long long)clock;
+    net->cache.view_dirty = true;            // the cells' gap-junction values are functions of the clock
     return SNN_OK;
 }
 ABI_CATCH
@@ -1201,12 +1181,7 @@ int snn_debug_checkpoint(snn_network_t *net, int restore) ABI_TRY
             HIP_TRY(hipMemcpyAsync(cp.arrays.back().second.data(), a.first, a.second, hipMemcpyDeviceToHost, net->stream), SNN_ERR_BUFFER_READ);
         }
         HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
-        cp.clock = net->clock; cp.st_clock = net->st_clock; cp.hist_steps = net->hist_steps; cp.hist_tick = net->hist_tick;
-        cp.shadow_cur = net->shadow_cur; cp.shadow_valid = net->shadow_valid; cp.cell_view_cur = net->cell_view_cur;
-        cp.view_dirty = net->view_dirty; cp.counts_dirty = net->counts_dirty; cp.uni_dirty = net->uni_dirty;
-        cp.live_mask_applied = net->live_mask_applied; cp.n_live = net->n_live;
-        for (int k = 0; k < K_TYPES; ++k) cp.live_type[k] = net->live_type[k];
-        cp.persistent_run = net->persistent_run; cp.mirror_mask = net->mirror_mask;
+        cp.st_clock = net->st_clock; cp.cur = net->cur; cp.cache = net->cache; cp.persistent_run = net->opt.persistent_run;
         cp.valid = true;
         return SNN_OK;
     }
@@ -1222,12 +1197,7 @@ int snn_debug_checkpoint(snn_network_t *net, int restore) ABI_TRY
     for (const auto &a : cp.arrays)
         HIP_TRY(hipMemcpyAsync(a.first, a.second.data(), a.second.size(), hipMemcpyHostToDevice, net->stream), SNN_ERR_BUFFER_WRITE);
     HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
-    net->clock = cp.clock; net->st_clock = cp.st_clock; net->hist_steps = cp.hist_steps; net->hist_tick = cp.hist_tick;
-    net->shadow_cur = cp.shadow_cur; net->shadow_valid = cp.shadow_valid; net->cell_view_cur = cp.cell_view_cur;
-    net->view_dirty = cp.view_dirty; net->counts_dirty = cp.counts_dirty; net->uni_dirty = cp.uni_dirty;
-    net->live_mask_applied = cp.live_mask_applied; net->n_live = cp.n_live;
-    for (int k = 0; k < K_TYPES; ++k) net->live_type[k] = cp.live_type[k];
-    net->persistent_run = cp.persistent_run; net->mirror_mask = cp.mirror_mask;
+    net->st_clock = cp.st_clock; net->cur = cp.cur; net->cache = cp.cache; net->opt.persistent_run = cp.persistent_run;
     net->stdp_pending = false; net->stdp_pending_rows_only = false; net->rstdp_pending = false; net->reward_since_defer = false;
     net->cells_stepped = false; net->local_inputs_done = false; net->run_tag = 1;
     if (net->run_granules) {
@@ -1245,7 +1215,7 @@ namespace {
 int run_steps(snn_network *net, uint64_t iterations)
 {
     uint64_t it = 0;
-    if (iterations >= 4 && net->external_stream && run_resident_shape(net)) net->stat_run_external_stream += 1;
+    if (iterations >= 4 && net->external_stream && run_resident_shape(net)) net->stat.run_external_stream += 1;
     // below 4 steps the launch's fixed cost (seed, weights into registers) shows
     while (iterations - it >= 4 && run_resident_applies(net)) {
         // The launch is a spin-wait all-to-all between workgroups that must all be resident.  A probe vouches for that
@@ -1255,11 +1225,11 @@ int run_steps(snn_network *net, uint64_t iterations)
         // handle then keeps.  The caller sees a slower call, never a half-stepped network.  The unit of the rollback is the
         // chunk (at most run_chunk_steps steps): what earlier chunks of the call committed -- the weights of STDP inside
         // the run among it -- is never replayed.
-        const uint64_t chunk = std::min<uint64_t>(iterations - it, std::max<uint32_t>(4u, net->run_chunk_steps));
-        const RunCursors saved = run_cursors(net);
+        const uint64_t chunk = std::min<uint64_t>(iterations - it, std::max<uint32_t>(4u, net->opt.run_resident_chunk_steps));
+        const RunCursors saved{net->cur, net->stat.run, net->ev_used};
         TRY(run_snapshot(net, /*restore=*/false));
         TRY(launch_run_resident(net, chunk, it));
-        if (!net->persistent_run) break;              // the co-residency probe said no, nothing was stepped
+        if (!net->opt.persistent_run) break;              // the co-residency probe said no, nothing was stepped
         HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
         if (net->run_failed && net->run_failed[0]) {
             net->run_failed[0] = 0u;
@@ -1267,11 +1237,11 @@ int run_steps(snn_network *net, uint64_t iterations)
             HIP_TRY(hipMemsetAsync(net->run_granules, 0, RUN_GRANULE_WORDS * 8, net->stream), SNN_ERR_BUFFER_WRITE);
             HIP_TRY(hipMemsetAsync(net->run_partials, 0, RUN_PARTIAL_WORDS * 8, net->stream), SNN_ERR_BUFFER_WRITE);
             net->run_tag = 1;
-            restore_cursors(net, saved);
-            net->shadow_valid = false;
-            net->view_dirty = true;
-            net->persistent_run = 0;
-            net->stat_run_fallbacks += 1;
+            net->cur = saved.cur; net->stat.run = saved.run; net->ev_used = saved.ev_used;
+            net->cache.shadow_valid = false;
+            net->cache.view_dirty = true;
+            net->opt.persistent_run = 0;
+            net->stat.run_fallbacks += 1;
             break;
         }
         it += chunk;
@@ -1753,7 +1723,7 @@ int snn_run_sharded_custom(snn_network_t *net, snn_exchange_fn exchange, void *u
         if (exchange(user, net->stream) != 0) return fail(SNN_ERR_QUEUE, "the caller's exchange function failed");
         TRY(refresh_unpack(net));
     }
-    if (net->halo_direct == 2 || exchange == &snn_exchange_noop) TRY(direct_begin(net));
+    if (net->opt.halo_direct == 2 || exchange == &snn_exchange_noop) TRY(direct_begin(net));
     int rc = SNN_OK;
     for (uint64_t it = 0; it < iterations && rc == SNN_OK; ++it) {
         if (net->nn) rc = step_begin(net);
@@ -1814,7 +1784,7 @@ static int agree_on_exchange(Rccl *R, snn_network *net, ncclComm_t comm, void *n
         for (uint32_t s = 0; s < net->x_planes; ++s) mask |= 1u << net->x_plane_id[s];
         // bit 30: this rank will step in the PEER form (connected, committed, "halo_peer" on).  A rank that is not, next to one
         // that is, would post ncclSend / ncclRecv nobody answers while the other polls granules nobody stores.
-        const bool peer_form = net->halo_peer && net->p2p_connected && net->p2p_recv[0] && net->peer_capable && net->halo_direct && net->csr_plan_direct &&
+        const bool peer_form = net->opt.halo_peer && net->p2p_connected && net->p2p_recv[0] && net->peer_capable && net->opt.halo_direct && net->csr_plan_direct &&
                                csr_fast_step(net);
         mask |= peer_form ? 0x40000000u : 0u;
         // bit 29: nothing travels to or from this rank (a lone shard, an empty one, rows that read no neighbour): it posts no
@@ -1947,7 +1917,7 @@ ABI_CATCH
 int snn_history_steps(const snn_network_t *net, uint64_t *steps) ABI_TRY
 {
     if (!net || !steps) return fail(SNN_ERR_BAD_ARG, "null argument");
-    *steps = net->hist_steps;
+    *steps = net->cur.hist_steps;
     return SNN_OK;
 }
 ABI_CATCH
@@ -1959,14 +1929,14 @@ int snn_get_voltage_history(snn_network_t *net, uint32_t id, float *dst, size_t 
     const LatticeInfo *l = find_lattice(net, id);
     if (!l) return fail(SNN_ERR_BAD_ARG, "unknown lattice id");
     if (!net->want_vhist) return fail(SNN_ERR_BAD_STATE, "voltage history is off");
-    if (count != net->hist_steps * l->count) return fail(SNN_ERR_DIM_MISMATCH, "history size mismatch");
+    if (count != net->cur.hist_steps * l->count) return fail(SNN_ERR_DIM_MISMATCH, "history size mismatch");
     if (count == 0) return SNN_OK;
     if (!dst) return fail(SNN_ERR_BAD_ARG, "dst is null");
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
     TRY(end_run(net));
     const float *src = l->spike_train ? net->st_vhist + (l->first - net->nn) : net->vhist + l->first;
     const size_t pitch = (size_t)(l->spike_train ? net->c_pad : net->n_pad) * 4;
-    HIP_TRY(copy2d_sync(net, dst, (size_t)l->count * 4, src, pitch, (size_t)l->count * 4, net->hist_steps, hipMemcpyDeviceToHost),
+    HIP_TRY(copy2d_sync(net, dst, (size_t)l->count * 4, src, pitch, (size_t)l->count * 4, net->cur.hist_steps, hipMemcpyDeviceToHost),
             SNN_ERR_BUFFER_READ);
     return SNN_OK;
 }
@@ -1979,15 +1949,15 @@ int snn_get_spike_history(snn_network_t *net, uint32_t id, uint8_t *dst, size_t 
     const LatticeInfo *l = find_lattice(net, id);
     if (!l || l->spike_train) return fail(SNN_ERR_BAD_ARG, "spike history exists for neuron lattices");
     if (!net->want_raster) return fail(SNN_ERR_BAD_STATE, "spike history is off");
-    if (count != net->hist_steps * l->count) return fail(SNN_ERR_DIM_MISMATCH, "history size mismatch");
+    if (count != net->cur.hist_steps * l->count) return fail(SNN_ERR_DIM_MISMATCH, "history size mismatch");
     if (count == 0) return SNN_OK;
     if (!dst) return fail(SNN_ERR_BAD_ARG, "dst is null");
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
     TRY(end_run(net));
     const size_t words = net->n_pad / 64;
-    hvec<unsigned long long> host(net->hist_steps * words);
+    hvec<unsigned long long> host(net->cur.hist_steps * words);
     HIP_TRY(copy_sync(net, host.data(), net->raster, host.size() * 8, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-    for (uint64_t s = 0; s < net->hist_steps; ++s)
+    for (uint64_t s = 0; s < net->cur.hist_steps; ++s)
         for (uint32_t i = 0; i < l->count; ++i) {
             const uint32_t q = l->first + i;
             dst[s * l->count + i] = (uint8_t)((host[s * words + (q >> 6)] >> (q & 63)) & 1ull);
@@ -2001,37 +1971,14 @@ int snn_set_option(snn_network_t *net, const char *name, int value) ABI_TRY
     if (!net || !name) return fail(SNN_ERR_BAD_ARG, "null argument");
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
     if (net->finalized) TRY(end_run(net));            // pending deferred updates belong to the old setting
-    const std::string n(name);
-    if (n == "fused_step") net->fused_step = value != 0;
-    else if (n == "pinned_copies") net->pinned_copies = (value >= 0 && value <= 2) ? value : 1;
-    else if (n == "dense_close") net->dense_close = value != 0;
-    else if (n == "cells_in_step") net->cells_in_step = value != 0;
-    else if (n == "update_packs") net->update_packs = value != 0;
-    else if (n == "update_all_planes") net->update_all_planes = (value >= 0 && value <= 3) ? value : 1;
-    else if (n == "persistent_stdp") net->persistent_stdp = value != 0;
-    else if (n == "halo_direct") net->halo_direct = (value >= 0 && value <= 2) ? value : 1;
-    else if (n == "halo_peer") { net->halo_peer = value != 0; net->x_agreed = false; }
-    else if (n == "halo_peer_delay") net->peer_delay = (uint32_t)std::max(0, std::min(value, 64));
-    else if (n == "halo_peer_spin_limit") net->p2p_spin_limit = value > 0 ? (uint32_t)value : (1u << 26);
-    else if (n == "csr_xcd_bands") net->csr_xcd_bands = value != 0;
-    else if (n == "csr_image") net->csr_image = value != 0;
-    else if (n == "resident_quarters") net->resident_quarters = value != 0;
-    else if (n == "defer_rstdp") net->defer_rstdp = value != 0;
-    else if (n == "defer_stdp") net->defer_stdp = (value >= 0 && value <= 3) ? value : 1;
-    else if (n == "uniform_params") { net->uniform_params = value != 0; net->uni_dirty = true; }
-    else if (n == "persistent_run") { net->persistent_run = value != 0; net->run_probed_grid = 0; }
-    else if (n == "persistent_chem") net->persistent_chem = value != 0;
-    else if (n == "run_resident_spin_limit") net->run_spin_limit = value > 0 ? (uint32_t)std::min<long long>(value, 0x7FFFFFFF) : RUN_RESIDENT_SPIN_LIMIT;
-    else if (n == "run_resident_fault_step") net->run_fault_step = (uint32_t)std::max<long long>(value, 0);
-    else if (n == "run_timing") net->run_timing_opt = value != 0;
-    else if (n == "input_shape") net->force_shape = (value == 1 || value == 2) ? value : 0;
-    else if (n == "stdp_columns_form") net->stdp_columns_form = value == 1 ? 1 : 0;
-    else if (n == "stdp_small") net->stdp_small = value != 0;
-    else if (n == "verify") net->verify = value != 0;
-    else if (n == "verify_fault") net->verify_fault = value > 0 ? (uint32_t)value : 0u;
-    else if (n == "run_resident_chunk_steps") net->run_chunk_steps = value >= 4 ? (uint32_t)std::min<long long>(value, 1 << 20) : (1u << 20);
-    else return fail(SNN_ERR_BAD_ARG, "unknown option '" + n + "'");
-    net->shadow_valid = false;
+    const OptionRow *r = std::find_if(std::begin(OPTION_TABLE), std::end(OPTION_TABLE),
+                                      [&](const OptionRow &o) { return o.source != ENV_ONLY && !strcmp(o.name, name); });
+    if (r == std::end(OPTION_TABLE)) return fail(SNN_ERR_BAD_ARG, "unknown option '" + std::string(name) + "'");
+    net->opt.*r->member = option_value(*r, value);
+    if (r->after == X_AGREED_FALSE) net->x_agreed = false;
+    if (r->after == UNI_DIRTY_TRUE) net->cache.uni_dirty = true;
+    if (r->after == RUN_PROBED_GRID_0) net->run_probed_grid = 0;
+    net->cache.shadow_valid = false;
     return SNN_OK;
 }
 ABI_CATCH
@@ -2039,35 +1986,9 @@ ABI_CATCH
 int snn_get_stat(snn_network_t *net, const char *name, uint64_t *value) ABI_TRY
 {
     if (!net || !name || !value) return fail(SNN_ERR_BAD_ARG, "null argument");
-    const std::string n(name);
-    if (n == "persistent_run_launches") *value = net->stat_run_launches;
-    else if (n == "persistent_run_steps") *value = net->stat_run_steps;
-    else if (n == "persistent_run_stdp_steps") *value = net->stat_run_stdp_steps;
-    else if (n == "persistent_run_fallbacks") *value = net->stat_run_fallbacks;
-    else if (n == "halo_direct_steps") *value = net->stat_direct_steps;
-    else if (n == "halo_peer_steps") *value = net->stat_peer_steps;
-    else if (n == "persistent_run_external_stream") *value = net->stat_run_external_stream;
-    else if (n == "steps_dense_one_launch") *value = net->stat_steps_dense_one_launch;
-    else if (n == "steps_dense_close") *value = net->stat_steps_dense_close;
-    else if (n == "steps_sparse_one_launch") *value = net->stat_steps_sparse_one_launch;
-    else if (n == "steps_sparse_image") *value = net->stat_steps_sparse_image;
-    else if (n == "image_staged_slices") *value = net->img_staged_slices;
-    else if (n == "image_staged_slices_direct") *value = net->img_staged_slices_direct;
-    else if (n == "steps_sparse_split") *value = net->stat_steps_sparse_split;
-    else if (n == "steps_two_kernel") *value = net->stat_steps_two_kernel;
-    else if (n == "shadow_refreshes") *value = net->stat_shadow_refreshes;
-    else if (n == "view_refreshes") *value = net->stat_view_refreshes;
-    else if (n == "history_regrows") *value = net->stat_history_regrows;
-    else if (n == "verify_runs") *value = net->stat_verify_runs;
-    else if (n == "verify_mismatches") *value = net->stat_verify_mismatches;
-    else if (n == "verify_skipped") *value = net->stat_verify_skipped;
-    else if (n == "run_timing_poll") *value = net->run_timing_last[0];
-    else if (n == "run_timing_barrier") *value = net->run_timing_last[1];
-    else if (n == "run_timing_turns") *value = net->run_timing_last[2];
-    else if (n == "run_timing_update") *value = net->run_timing_last[3];
-    else if (n == "run_timing_steps") *value = net->run_timing_steps;
-    else return fail(SNN_ERR_BAD_ARG, "unknown statistic '" + n + "'");
-    return SNN_OK;
+    for (const StatRow &r : STAT_TABLE)
+        if (!strcmp(r.name, name)) { *value = r.read(*net); return SNN_OK; }
+    return fail(SNN_ERR_BAD_ARG, "unknown statistic '" + std::string(name) + "'");
 }
 ABI_CATCH
 
@@ -2118,7 +2039,7 @@ int snn_set_synthetic_drive(snn_network_t *net, uint64_t seed, float fraction, f
     net->drive_seed = seed;
     net->drive_threshold = (uint32_t)std::min<double>(4294967295.0, (double)fraction * 4294967296.0);
     net->drive_voltage = voltage;
-    net->shadow_valid = false;
+    net->cache.shadow_valid = false;
     return SNN_OK;
 }
 ABI_CATCH
@@ -2140,14 +2061,14 @@ int snn_input_kernel_bytes(const snn_network_t *net, uint64_t *bytes) ABI_TRY
         uint64_t per_neuron = net->model == SNN_MODEL_CUSTOM ? (uint64_t)8 * custom::NVARS + 28
                                                             : S_MODEL[net->model == SNN_MODEL_BCM_IZHIKEVICH ? 0 : net->model & 7];
         if (net->model == SNN_MODEL_BCM_IZHIKEVICH) per_neuron += 36;       // activities, window clock, period, spike count
-        if (net->chemical) per_neuron += (uint64_t)44 * net->n_live;
+        if (net->chemical) per_neuron += (uint64_t)44 * net->cache.n_live;
         *bytes = (uint64_t)8 * net->nnz + (fused_csr_step_applies(net) ? per_neuron * net->n_owned : 0u);
         if (fused_csr_step_applies(net) && cells_ride_allowed(net))
             *bytes += (uint64_t)28 * (net->cell_list_dev ? net->n_cells_listed : net->nc);
         return SNN_OK;
     }
     uint64_t b = (uint64_t)4 * net->n_tot * net->n_loc;                    // dense: every weight of the shard, read once
-    if (net->any_modulation && net->defer_rstdp) {
+    if (net->any_modulation && net->opt.defer_rstdp) {
         // k_inputs_rstdp: the internal edges of a reward-modulated lattice are read AND rewritten, weight and trace --
         // 16 B per synapse instead of 4
         for (const auto &l : net->lattices) {

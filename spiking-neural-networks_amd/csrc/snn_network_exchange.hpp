@@ -266,9 +266,9 @@ WireArgs wire_args(snn_network *net, int which, int set)
     a.list = halo ? (which == 0 ? net->halo_send_idx.get() : net->halo_recv_idx.get()) : nullptr;
     a.skip = (!halo && which == 1) ? net->shard_index : 0xFFFFFFFFu;
     a.last_firing_time = net->na.last_firing_time;
-    a.clock = net->clock;
+    a.clock = net->cur.clock;
     // sparse handles stepping with k_step_csr read S(t) from a shadow of the mirror: what arrives goes there too
-    a.xbuf2 = (which == 1 && net->csr && net->shadow_valid) ? net->shadow[net->shadow_cur] : nullptr;
+    a.xbuf2 = (which == 1 && net->csr && net->cache.shadow_valid) ? net->shadow[net->cache.shadow_cur] : nullptr;
     return a;
 }
 
@@ -302,7 +302,7 @@ int launch_step_close(snn_network *net, bool cells, bool unpack)
 {
     StepCloseArgs a{};
     uint32_t cell_work = 0;
-    if (cells) cell_work = spike_train_args(net, a.cells, 1, net->run_step_offset, net->clock + 1);
+    if (cells) cell_work = spike_train_args(net, a.cells, 1, net->cur.run_step_offset, net->cur.clock + 1);
     a.cell_blocks = (cell_work + 255) / 256;
     if (unpack && net->n_shards > 1 && net->seg_n[1] && net->recv_total) {
         a.recv = wire_args(net, 1);
@@ -483,7 +483,7 @@ uint32_t plan_plane_mask(const snn_network *net)
 }
 bool mirror_stale(const snn_network *net)
 {
-    return net->sharded && net->n_shards > 1 && (plan_plane_mask(net) & ~net->mirror_mask) != 0;
+    return net->sharded && net->n_shards > 1 && (plan_plane_mask(net) & ~net->cache.mirror_mask) != 0;
 }
 int refresh_pack(snn_network *net)
 {
@@ -497,11 +497,11 @@ int refresh_unpack(snn_network *net)
 {
     if (net->seg_n[1] && net->seg_max[1] && net->nn) {
         WireArgs a = wire_args(net, 1);
-        a.clock = net->clock - 1;                                 // the step whose spike flags are restated
+        a.clock = net->cur.clock - 1;                                 // the step whose spike flags are restated
         hipLaunchKernelGGL(k_exchange_unpack, dim3((net->seg_max[1] + 255) / 256, net->seg_n[1]), dim3(256), 0, net->stream, a);
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
     }
-    net->mirror_mask |= plan_plane_mask(net);
+    net->cache.mirror_mask |= plan_plane_mask(net);
     return SNN_OK;
 }
 
@@ -512,8 +512,8 @@ int direct_begin(snn_network *net)
 {
     net->direct_run = false;
     net->peer_run = false;
-    if (!net->halo_direct || !csr_fast_step(net) || net->n_shards < 2 || !net->csr_plan_direct) return SNN_OK;
-    const bool peer = net->halo_peer && net->peer_capable && net->p2p_connected && net->p2p_recv[0];
+    if (!net->opt.halo_direct || !csr_fast_step(net) || net->n_shards < 2 || !net->csr_plan_direct) return SNN_OK;
+    const bool peer = net->opt.halo_peer && net->peer_capable && net->p2p_connected && net->p2p_recv[0];
     if (!net->direct_capable && !peer) return SNN_OK;        // (several planes on the wire: only the peer form gathers them itself)
     uint64_t so = 0;
     for (uint32_t p = 0; p < net->n_shards; ++p) so += net->x_send_words[p];
@@ -553,18 +553,18 @@ int direct_end(snn_network *net)
         // the last step's arrivals (granules of set (epoch - 1) % 2, tagged epoch) into the mirror and the current shadow
         StepCloseArgs c{};
         c.recv = wire_args(net, 1);
-        c.recv.clock = net->clock - 1;
+        c.recv.clock = net->cur.clock - 1;
         c.xbuf2 = c.recv.xbuf2;
         c.recv_total = net->recv_total; c.recv_segments = net->seg_n[1];
         c.unpack_blocks = (net->recv_total + 255) / 256;
         c.recv64 = net->p2p_recv[(net->p2p_epoch + 1u) & 1u]; c.recv_tag = net->p2p_epoch;
-        c.spin_limit = net->p2p_spin_limit; c.failed = PeerFailure{{net->p2p_failed, net->p2p_done_blocks + 1}};
+        c.spin_limit = net->opt.halo_peer_spin_limit; c.failed = PeerFailure{{net->p2p_failed, net->p2p_done_blocks + 1}};
         if (c.unpack_blocks) hipLaunchKernelGGL(k_step_close, dim3(c.unpack_blocks), dim3(256), 0, net->stream, c);
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
         return SNN_OK;
     }
     WireArgs a = wire_args(net, 1, net->hx_par ^ 1);              // the set the last step's exchange filled
-    a.clock = net->clock - 1;
+    a.clock = net->cur.clock - 1;
     hipLaunchKernelGGL(k_exchange_unpack, dim3((net->seg_max[1] + 255) / 256, net->seg_n[1]), dim3(256), 0, net->stream, a);
     HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
     return SNN_OK;

@@ -28,6 +28,7 @@
 #include "snn_kernels_resident.hpp"
 #include "snn_kernels_update.hpp"
 #include "snn_layout.hpp"
+#include "snn_options.hpp"
 
 using namespace snn;
 
@@ -180,17 +181,51 @@ struct LatticeInfo {
     bool spike_train;
 };
 
+// Host-side cursors a run moves: what a rollback, the second pass of "verify" and a checkpoint put back, by assignment.
+struct Cursors {
+    long long clock = 0, run_step_offset = 0;        // (the steps of the open run the spike-train lattices' host clocks do not hold yet)
+    uint64_t hist_steps = 0, hist_tick = 0;          // history rows stored, steps seen since the record was (re)started
+};
+// Which caches of the handle are current; a checkpoint carries it whole.
+struct CacheState {
+    int shadow_cur = 0, cell_view_cur = 0;
+    bool shadow_valid = false;             // shadow[shadow_cur] == exchange buffer
+    bool view_dirty = true;                // spike-train gap-junction values must be refreshed before the next inputs
+    bool counts_dirty = true, uni_dirty = true;      // the static per-column counts / the uniform-parameter tables must be rescanned
+    // live transmitter types of the handle (the union over its lattices), refreshed with the static counts: the dense
+    // input pass is specialised on their number and leaves the partial planes of the other types untouched (zero)
+    uint32_t live_mask_applied = 0xFFFFFFFFu, n_live = K_TYPES, live_type[K_TYPES] = {0, 1, 2};
+    // planes (bit = plane id) whose values of the neurons owned ELSEWHERE are current in this handle's mirror: everything after
+    // the attributes were written, then only what the exchange carried.  A plan that needs more (a synapse kind switched on
+    // between two runs) calls for one exchange of the current state before the next step (refresh_*, snn_network_exchange.hpp)
+    uint32_t mirror_mask = 0xFFFFFFFFu;
+};
+// The counters behind snn_get_stat (STAT_TABLE, below the handle).
+struct Stats {
+    struct Run { uint64_t launches = 0, steps = 0, stdp_steps = 0; } run;      // of the one-launch run; a rollback takes them back
+    uint64_t run_fallbacks = 0, run_external_stream = 0;      // (run calls that kept one launch per step only because the handle runs on a caller's stream)
+    uint64_t direct_steps = 0, peer_steps = 0;
+    // which form each step took: k_step_resident, k_inputs_dense_close, k_step_csr whole (from the step image), border + interior, input pass + k_update
+    uint64_t steps_dense_one_launch = 0, steps_dense_close = 0, steps_sparse_one_launch = 0, steps_sparse_image = 0;
+    uint64_t steps_sparse_split = 0, steps_two_kernel = 0;
+    uint64_t shadow_refreshes = 0, view_refreshes = 0, history_regrows = 0;
+    uint64_t verify_runs = 0, verify_mismatches = 0, verify_skipped = 0;
+};
+
 } // namespace
 
 struct snn_network {
     int device = 0;
+    Options opt;                           // the tuning switches (snn_options.hpp)
+    Stats stat;
+    Cursors cur;
+    CacheState cache;
     hipStream_t stream = nullptr;          // the stream every launch goes to
     hipStream_t own_stream = nullptr;      // created with the handle
     bool external_stream = false;          // snn_set_stream adopted a caller's stream
     int model = 0, nt_kind = 0, rc_kind = 0, st_kind = 0;
     bool finalized = false;
     int electrical = 1, chemical = 0;
-    long long clock = 0;
 
     hvec<LatticeInfo> lattices;      // neuron lattices, ascending id after finalize
     hvec<LatticeInfo> st_lattices;   // spike-train lattices
@@ -201,10 +236,6 @@ struct snn_network {
     std::map<uint32_t, bool> lattice_has_nt;    // lattice id -> some neurotransmitters$flags entry is set
     bool any_nt_neurons = false, any_nt_cells = false;
     std::map<uint32_t, uint32_t> lattice_nt_mask;   // lattice id -> bit k: some cell of it releases transmitter type k
-    // live transmitter types of the handle (the union over its lattices), refreshed with the static counts: the dense
-    // input pass is specialised on their number and leaves the partial planes of the other types untouched (zero)
-    uint32_t n_live = K_TYPES, live_type[K_TYPES] = {0, 1, 2};
-    uint32_t live_mask_applied = 0xFFFFFFFFu;
     // reward modulation (RewardModulatedLattice): per-lattice modulator table + per-edge trace, allocated on first use
     bool any_modulation = false;           // some lattice has do_modulation set
     bool any_modulated = false;            // some lattice is a reward-modulated lattice (modulating or paused): rewards reach its modulator
@@ -225,7 +256,6 @@ struct snn_network {
     bool cross_checked = false;           // the connection kinds lie where the reference defines their updates (check_reward_cross)
     // Dense handles defer the weight update of step t to the input pass of step t+1 (k_inputs_rstdp: one pass over
     // W and the traces instead of two); any host access to weights / traces / timing flushes it first.
-    int defer_rstdp = 1;                   // 0: always the standalone pass (SNN_AMD_DEFER_RSTDP=0)
     bool rstdp_pending = false;
     bool reward_since_defer = false;       // a reward was applied after the deferral: use RM_DOPAMINE_BEFORE
 
@@ -249,10 +279,6 @@ struct snn_network {
     RowMap rowmap{};
     // ---- exchange plan (snn_kernels_exchange.hpp), rebuilt by ensure_exchange_plan when x_dirty ----
     bool x_dirty = true;
-    // planes (bit = plane id) whose values of the neurons owned ELSEWHERE are current in this handle's mirror: everything after
-    // the attributes were written, then only what the exchange carried.  A plan that needs more (a synapse kind switched on
-    // between two runs) calls for one exchange of the current state before the next step (refresh_*, snn_network_exchange.hpp)
-    uint32_t mirror_mask = 0xFFFFFFFFu;
     bool x_agreed = false;                      // the ranks of the communicator compared their plans (snn_run_sharded)
     bool refresh_agreed = false;                // ... and some rank's mirror lacked a plane: all refresh before the next run's first step
     int x_mode = SNN_EXCHANGE_ALLGATHER;
@@ -279,9 +305,6 @@ struct snn_network {
     uint32_t recv_total = 0, send_bitmap_words = 0;
     bool send_bits_clean = true;          // every outgoing spike bitmap is zero (what the in-kernel pack ORs into)
     bool update_packed = false;           // this step's own slot of the all-gather buffer was written by k_update
-    int update_packs = 1;                 // option "update_packs"
-    bool resident_quarters = true;        // option "resident_quarters": the one-launch step with a chunk's rows over four wavefronts
-    int update_all_planes = 1;            // option "update_all_planes": 1 all planes' partials in one thread (default), 2 / 3 the wide update (k_update_wide; measured slower)
     bool step_packed = false;             // this step's outgoing segments were written by k_step_csr itself
     bool interior_pending = false;        // the border half of this step is enqueued, the interior slices are not yet
     // Library-driven runs of such a handle (snn_run_sharded): the rows gather the halo from the received segments themselves
@@ -294,13 +317,10 @@ struct snn_network {
     dev_ptr<uint32_t> csr_plan_direct, halo_word_dev;
     bool direct_capable = false;          // the plan has the direct form (sparse, halo mode, voltage the only plane)
     bool peer_capable = false;            // the plan has the PEER form (sparse, halo mode, any planes)
-    uint32_t peer_delay = 0;              // option "halo_peer_delay": injected latencies, in s_sleep(127) units (tests)
     bool direct_run = false;              // ... and the run in progress uses it
     int hx_par = 0;
     bool stamp_pending = false;
-    uint64_t stat_direct_steps = 0;       // statistic "halo_direct_steps"
     bool tail_done = false;               // this step's jobs behind the rows are enqueued
-    int halo_direct = 1;                  // option "halo_direct": 0 never, 1 snn_run_sharded, 2 also snn_run_sharded_custom
     // PEER form of such a run (snn_network_exchange.hpp): the border rows store {value, tag | spike} granules straight into the
     // peers' receive sets, the rows of the next step read them when their tag says so, and a done counter per peer says when a
     // set may be overwritten -- no collective, ONE launch per step.  Needs the peers' addresses (snn_p2p_connect / _commit).
@@ -321,9 +341,6 @@ struct snn_network {
     hvec<dev_ptr<void>> p2p_retired;                   // receive sets / done counters of earlier plans, see p2p_release
     bool peer_run = false;                                    // the run in progress uses the peer form
     uint32_t p2p_epoch = 0;                                   // steps of peer-form runs done so far (tags and done counters)
-    uint32_t p2p_spin_limit = 1u << 26;
-    int halo_peer = 1;                                        // option "halo_peer": 0 keeps the collective even when connected
-    uint64_t stat_peer_steps = 0;                             // statistic "halo_peer_steps"
     // in-library collective (snn_run_sharded): RCCL is ordered on its own stream against the compute stream
     hipStream_t comm_stream = nullptr;
     hipEvent_t ev_packed = nullptr, ev_exchanged = nullptr;
@@ -345,7 +362,6 @@ struct snn_network {
     float *xbuf = nullptr;
     float *part_i = nullptr, *part_t = nullptr;
     uint32_t *n_in = nullptr, *tcount = nullptr;
-    bool counts_dirty = true;
     NeuronArrays na{};
     CellArrays ca{};
     uint32_t *lattice_slot = nullptr;
@@ -366,7 +382,7 @@ struct snn_network {
     dev_ptr<uint32_t> csr_img_hdr, csr_plan_win;
     dev_ptr<uint4> csr_img_rec;
     uint64_t img_records = 0, img_staged_slices = 0;
-    bool img_stale = true, csr_image = true;      // csr_image: option "csr_image"
+    bool img_stale = true;
     // ... and its twin for the runs of a shard handle whose rows gather the halo from the received segments (csr_plan_direct):
     // the same graph with every halo neuron's source moved to its word of the receive buffer; built with the exchange plan
     dev_ptr<uint32_t> csr_img_hdr_direct, csr_plan_win_direct;
@@ -375,36 +391,17 @@ struct snn_network {
     bool img_stale_direct = true;
     hvec<uint32_t> sell_pre_host, slice_ptr_host;     // the SELL indices as set (shard handles: the direct image is built from them)
     uint2 *cell_view[2] = {nullptr, nullptr};
-    int cell_view_cur = 0;
     bool cells_stepped = false;      // this step's cells advanced inside k_step_csr (step_end skips their launch)
-    int csr_xcd_bands = 1;           // option "csr_xcd_bands"
-    int cells_in_step = 1;           // option "cells_in_step": 0 keeps the cells in their own launch
     // uniform-parameter tables (UniformTable, snn_layout.hpp): rescanned when attributes were set
     UniformTable *uni_neuron = nullptr, *uni_cell = nullptr;
-    bool uni_dirty = true;
-    int uniform_params = 1;               // 0: always read the arrays (SNN_AMD_UNIFORM_PARAMS=0)
     // many steps of a small lattice in one launch (k_run_resident): granule slots, the next free step tag, and a
     // host-visible word the kernel sets when its workgroups could not see each other
-    int persistent_run = 1;               // 0: one launch per step (SNN_AMD_PERSISTENT_RUN=0)
-    int persistent_chem = 1;              // option "persistent_chem": 0 keeps networks with chemical synapses on the per-step forms
     unsigned long long *run_granules = nullptr;
     unsigned long long *run_partials = nullptr;
     uint32_t run_tag = 1;
     float *run_w_out = nullptr;           // STDP inside the one-launch run: where the workgroups leave their weights (layout of W)
-    int persistent_stdp = 1;              // option "persistent_stdp"
-    uint64_t stat_run_stdp_steps = 0;
     pinned_ptr<uint32_t> run_failed;      // hipHostMalloc: [0] a run gave up, [1] the co-residency probe said no
     uint32_t run_probed_grid = 0;         // grid size the probe last vouched for
-    uint64_t stat_run_launches = 0, stat_run_steps = 0, stat_run_fallbacks = 0;
-    uint64_t stat_run_external_stream = 0;      // run calls that kept one launch per step only because the handle runs on a caller's stream
-    // which form each step took (statistics "steps_*"): k_step_resident, k_step_csr whole, k_step_csr border + interior,
-    // input pass + k_update
-    uint64_t stat_steps_sparse_image = 0;
-    uint64_t stat_steps_dense_one_launch = 0, stat_steps_sparse_one_launch = 0, stat_steps_sparse_split = 0, stat_steps_two_kernel = 0;
-    uint64_t stat_steps_dense_close = 0;         // streamed dense steps whose input pass also updated the neurons (k_inputs_dense_close)
-    uint64_t stat_shadow_refreshes = 0, stat_view_refreshes = 0, stat_history_regrows = 0;
-    uint32_t run_spin_limit = RUN_RESIDENT_SPIN_LIMIT;   // option "run_resident_spin_limit"
-    uint32_t run_fault_step = 0;                         // option "run_resident_fault_step" (test hook, see ResidentRunArgs)
     // every small device array of the handle (all per-neuron / per-cell state, the exchange buffer and its shadows, the
     // device clocks) is copied aside in ONE launch before a one-launch run and copied back if the run gave up
     CopyEntry *snap_table = nullptr;
@@ -414,46 +411,28 @@ struct snn_network {
     size_t snap_words = 0;
     hvec<CopyEntry> snap_table_host;     // the table as uploaded (names of the arrays in a "verify" report)
     size_t verify_words = 0;                    // capacity of each half of verify_buf
-    uint32_t run_chunk_steps = 1u << 20;        // option "run_resident_chunk_steps" (test hook): steps per one-launch chunk
-    // option "verify" (SNN_AMD_VERIFY=1; tests and campaigns): every snn_run call on a handle without weight updates takes its
-    // steps TWICE from the same snapshot and compares the two outcomes on the device (k_compare_table_alt)
-    int verify = 0;
-    uint32_t verify_fault = 0;                  // option "verify_fault" (test hook): word + 1 of the exchange buffer (2^30 + word of the weights) to disturb once
-    uint32_t *verify_buf = nullptr;             // the first outcome, laid out like snap_buf
+    uint32_t *verify_buf = nullptr;             // option "verify": the first outcome, laid out like snap_buf
     dev_ptr<uint32_t> verify_report;            // device words, see k_compare_table_alt
-    int pinned_copies = 1;                      // option "pinned_copies" [1]: see copy_sync (SNN_AMD_PINNED_COPIES=0: the runtime stages pageable pointers itself)
-    pinned_ptr<char> copy_stage;                // its page-locked staging buffer (8 MiB, allocated with the first such copy)
+    pinned_ptr<char> copy_stage;                // option "pinned_copies": the page-locked staging buffer (8 MiB, allocated with the first such copy)
     dev_ptr<uint32_t> verify_third;             // on a mismatch: the second outcome, while a third execution decides which one repeats
     size_t verify_third_words = 0;
     dev_ptr<char> verify_big;                   // runs with weight updates: [the matrices at the start | after the first pass]
     size_t verify_big_bytes = 0;
     uint64_t snap_generation = 0;               // how often the snapshot table has been laid out
-    uint64_t stat_verify_runs = 0, stat_verify_mismatches = 0, stat_verify_skipped = 0;
     std::string verify_text;                    // what the last mismatch was (snn_debug_verify_report)
-    // snn_debug_checkpoint (test support): device arrays and the stepper's host-side cursors as they were at the call
+    // snn_debug_checkpoint (test support): device arrays and the stepper's host-side state as they were at the call
     struct Checkpoint {
         bool valid = false;
         hvec<std::pair<void *, hvec<uint8_t>>> arrays;
-        long long clock = 0;
         hvec<long long> st_clock;
-        uint64_t hist_steps = 0, hist_tick = 0;
-        int shadow_cur = 0, cell_view_cur = 0, persistent_run = 1;
-        bool shadow_valid = false, view_dirty = true, counts_dirty = true, uni_dirty = true;
-        uint32_t live_mask_applied = 0xFFFFFFFFu, n_live = K_TYPES, live_type[K_TYPES] = {0, 1, 2}, mirror_mask = 0xFFFFFFFFu;
+        Cursors cur;
+        CacheState cache;
+        uint32_t persistent_run = 1;
     } checkpoint;
-    unsigned long long *run_timing = nullptr;   // SNN_AMD_RUN_TIMING=1: phase clocks of k_run_resident, printed per launch
-    int run_timing_opt = 0;                     // option "run_timing": collect them without printing (snn_get_stat)
+    unsigned long long *run_timing = nullptr;   // SNN_AMD_RUN_TIMING=1 or option "run_timing": phase clocks of k_run_resident
     unsigned long long run_timing_last[4] = {0, 0, 0, 0};   // workgroup 0, last launch: poll, barrier, turns, update + publish
     uint32_t run_timing_steps = 0;
-    int force_shape = 0;                  // 1 | 2: streamed shape of the dense input pass (SNN_AMD_INPUT_SHAPE), 0: by size
-    // deferred STDP (dense handles): the update of step t is applied by the input pass of step t + 1
-    // 0 (default): the scatter kernels right after the step; 1: the update of step t rides on the input pass of step
-    // t + 1; 2: prepared delta vectors, applied right away by scatter passes (SNN_AMD_DEFER_STDP / "defer_stdp").
-    // Measured on the quad-row matrix: the scatter kernels win at every spike rate.
-    int defer_stdp = 0;
-    int stdp_small = 1;                   // option "stdp_small": networks of <= 1024 rows take compaction + both scatters in ONE launch (k_stdp_small)
-    int stdp_columns_form = 0;            // option "stdp_columns_form": 0 one thread per presynaptic row, 1 one lane per 16-byte unit (k_stdp_columns_quads)
-    bool stdp_pending = false;
+    bool stdp_pending = false;            // deferred STDP (option "defer_stdp"): the update of the step just closed is still to be applied
     bool stdp_pending_rows_only = false;   // ... and it is the ROW half only ("defer_stdp" 3)
     uint32_t *stdp_rowbits = nullptr;       // [n_chunks][8] one bit per presynaptic row that spiked in the step just closed
     uint32_t *stdp_flag = nullptr;
@@ -461,18 +440,11 @@ struct snn_network {
     uint32_t dcol_stride = 0;
     long long *st_clock_dev = nullptr;
     pinned_ptr<long long> st_clock_pinned;  // page-locked staging of st_clock for the asynchronous upload that opens a run
-    long long run_step_offset = 0;
     bool run_active = false;        // a (possibly externally driven) run is open: device clocks are ahead of st_clock
     // fused small-lattice step (k_step_resident): two shadow copies of the exchange buffer + per-tile tickets
     float *shadow[2] = {nullptr, nullptr};
-    int shadow_cur = 0;
-    bool shadow_valid = false;      // shadow[shadow_cur] == exchange buffer
-    int fused_step = 1;             // 0: always take the two-kernel path (SNN_AMD_FUSED_STEP=0)
-    int dense_close = 0;            // 1: streamed dense matrices: the last workgroup of a column tile updates its neurons (measured: slower than two kernels)
-    uint32_t dense_close_max_chunks = 1u << 30;   // ... only up to this many chunks of presynaptic rows (SNN_AMD_DENSE_CLOSE_MAX_CHUNKS; experiments)
     uint32_t *tile_done = nullptr;  // k_inputs_dense_close: per column tile, the workgroups that have stored their partials (0 between launches)
     uint32_t tile_done_len = 0;
-    bool view_dirty = true;         // spike-train gap-junction values must be refreshed before the next inputs
     bool local_inputs_done = false; // this step's LOCAL chunk partials are already enqueued
 
     std::map<std::string, Attr> neuron_attrs, cell_attrs;
@@ -488,11 +460,10 @@ struct snn_network {
     float eeg_ref = 0.007f, eeg_dist = 0.8f, eeg_cond = 251.0f;     // EEGHistory defaults, neuron/mod.rs:246-255
     dev_ptr<float> summ_avg, summ_eeg;                              // [cap][n_lattices]
     uint32_t *spike_counts = nullptr, *lat_first_dev = nullptr, *lat_count_dev = nullptr;
-    uint64_t hist_steps = 0, hist_cap = 0;
+    uint64_t hist_cap = 0;
     hvec<hvec<float>> preset_host;   // PresetSpikeTrain firing times per cell
     dev_ptr<float> preset_times_dev;
-    uint64_t hist_tick = 0;                // steps seen since the record was (re)started
-    uint32_t hist_every = 1;               // a row is stored when hist_tick % hist_every == 0
+    uint32_t hist_every = 1;               // a row is stored when cur.hist_tick % hist_every == 0
     dev_ptr<float> vhist, st_vhist;
     dev_ptr<unsigned long long> raster;
 
@@ -515,6 +486,40 @@ struct snn_network {
 };
 
 namespace {
+static_assert(Options{}.run_resident_spin_limit == RUN_RESIDENT_SPIN_LIMIT, "snn_options.hpp restates the kernel header's default");
+
+struct StatRow { const char *name; uint64_t (*read)(const snn_network &); };
+#define STAT(field) [](const snn_network &n) -> uint64_t { return n.field; }
+const StatRow STAT_TABLE[] = {
+    {"persistent_run_launches", STAT(stat.run.launches)},
+    {"persistent_run_steps", STAT(stat.run.steps)},
+    {"persistent_run_stdp_steps", STAT(stat.run.stdp_steps)},
+    {"persistent_run_fallbacks", STAT(stat.run_fallbacks)},
+    {"persistent_run_external_stream", STAT(stat.run_external_stream)},
+    {"halo_direct_steps", STAT(stat.direct_steps)},
+    {"halo_peer_steps", STAT(stat.peer_steps)},
+    {"steps_dense_one_launch", STAT(stat.steps_dense_one_launch)},
+    {"steps_dense_close", STAT(stat.steps_dense_close)},
+    {"steps_sparse_one_launch", STAT(stat.steps_sparse_one_launch)},
+    {"steps_sparse_image", STAT(stat.steps_sparse_image)},
+    {"steps_sparse_split", STAT(stat.steps_sparse_split)},
+    {"steps_two_kernel", STAT(stat.steps_two_kernel)},
+    {"shadow_refreshes", STAT(stat.shadow_refreshes)},
+    {"view_refreshes", STAT(stat.view_refreshes)},
+    {"history_regrows", STAT(stat.history_regrows)},
+    {"verify_runs", STAT(stat.verify_runs)},
+    {"verify_mismatches", STAT(stat.verify_mismatches)},
+    {"verify_skipped", STAT(stat.verify_skipped)},
+    {"image_staged_slices", STAT(img_staged_slices)},
+    {"image_staged_slices_direct", STAT(img_staged_slices_direct)},
+    {"run_timing_poll", STAT(run_timing_last[0])},
+    {"run_timing_barrier", STAT(run_timing_last[1])},
+    {"run_timing_turns", STAT(run_timing_last[2])},
+    {"run_timing_update", STAT(run_timing_last[3])},
+    {"run_timing_steps", STAT(run_timing_steps)},
+};
+#undef STAT
+
 inline bool recording(const snn_network *net)
 {
     return net->want_vhist || net->want_raster || net->want_avg || net->want_eeg || net->any_whist;
@@ -522,7 +527,7 @@ inline bool recording(const snn_network *net)
 // does the step being computed store its history rows (strided capture: every hist_every-th step)
 inline bool record_now(const snn_network *net)
 {
-    return recording(net) && net->hist_tick % net->hist_every == 0;
+    return recording(net) && net->cur.hist_tick % net->hist_every == 0;
 }
 } // namespace
 
@@ -570,7 +575,7 @@ inline hipError_t snn_malloc(dev_ptr<T> *out, size_t bytes)
 // memory overwritten by what looks like a spike-raster word, another with a voltage history that did not match its own final state).
 inline hipError_t copy_sync(snn_network *net, void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
 {
-    if (net->pinned_copies && bytes && (kind == hipMemcpyDeviceToHost || kind == hipMemcpyHostToDevice)) {
+    if (net->opt.pinned_copies && bytes && (kind == hipMemcpyDeviceToHost || kind == hipMemcpyHostToDevice)) {
         constexpr size_t STAGE = (size_t)8 << 20;
         if (!net->copy_stage) {
             const hipError_t e = host_malloc(&net->copy_stage, STAGE, hipHostMallocDefault);
@@ -596,7 +601,7 @@ inline hipError_t copy_sync(snn_network *net, void *dst, const void *src, size_t
 inline hipError_t copy2d_sync(snn_network *net, void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height,
                               hipMemcpyKind kind)
 {
-    if (net->pinned_copies >= 2 && width && height && (kind == hipMemcpyDeviceToHost || kind == hipMemcpyHostToDevice)) {
+    if (net->opt.pinned_copies >= 2 && width && height && (kind == hipMemcpyDeviceToHost || kind == hipMemcpyHostToDevice)) {
         constexpr size_t STAGE = (size_t)8 << 20;
         if (width > STAGE) return hipErrorInvalidValue;
         if (!net->copy_stage) {
@@ -1117,7 +1122,7 @@ int build_state(snn_network *net)
     TRY(dev_alloc_t(net, &net->part_t, (size_t)K_TYPES * net->n_chunks * net->ld));
     TRY(dev_alloc_t(net, &net->n_in, net->ld));
     TRY(dev_alloc_t(net, &net->tcount, (size_t)K_TYPES * net->ld));
-    net->counts_dirty = true;
+    net->cache.counts_dirty = true;
     HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
     return SNN_OK;
 }
@@ -1162,9 +1167,9 @@ int attr_io(snn_network *net, uint32_t id, const char *name, AttrType type, void
     if (l->count == 0) return SNN_OK;
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
     TRY(end_run(net));
-    if (set && l->spike_train) net->view_dirty = true;
-    if (set) net->shadow_valid = false;
-    if (set) net->uni_dirty = true;
+    if (set && l->spike_train) net->cache.view_dirty = true;
+    if (set) net->cache.shadow_valid = false;
+    if (set) net->cache.uni_dirty = true;
     const uint32_t first = l->spike_train ? l->first - net->nn : l->first;   // index inside its own arrays
 
     if (!typed) {
@@ -1191,7 +1196,7 @@ int attr_io(snn_network *net, uint32_t id, const char *name, AttrType type, void
             if (!set) for (uint32_t i = 0; i < l->count; ++i) h[(size_t)i * K_TYPES + k] = tmp[i];
         }
     }
-    if (set && a.dirties) net->counts_dirty = true;
+    if (set && a.dirties) net->cache.counts_dirty = true;
     if (set && a.dirties && type == T_U32 && typed) {
         // "neurotransmitters$flags": remember which lattices release anything at all, so that networks without
         // neurotransmitters do not read three flag planes per neuron / cell and step
@@ -1300,11 +1305,11 @@ SellGraph csr_graph(const snn_network *net)
 // Which read-only parameters hold one value for the whole population (UniformTable): rescanned after attribute writes
 int ensure_uniform_tables(snn_network *net)
 {
-    if (!net->uni_dirty) return SNN_OK;
-    net->uni_dirty = false;
+    if (!net->cache.uni_dirty) return SNN_OK;
+    net->cache.uni_dirty = false;
     HIP_TRY(hipMemsetAsync(net->uni_neuron, 0, sizeof(UniformTable), net->stream), SNN_ERR_BUFFER_WRITE);
     HIP_TRY(hipMemsetAsync(net->uni_cell, 0, sizeof(UniformTable), net->stream), SNN_ERR_BUFFER_WRITE);
-    if (!net->uniform_params) return SNN_OK;
+    if (!net->opt.uniform_params) return SNN_OK;
     auto scan = [&](UniformTable *t, int slot, const void *arr, uint32_t n) -> int {
         if (n == 0 || !arr) return SNN_OK;
         const uint32_t *p = static_cast<const uint32_t *>(arr);
@@ -1328,21 +1333,21 @@ int ensure_uniform_tables(snn_network *net)
 
 int ensure_counts(snn_network *net)
 {
-    if (!net->counts_dirty || net->n_loc == 0) { net->counts_dirty = false; return SNN_OK; }
+    if (!net->cache.counts_dirty || net->n_loc == 0) { net->cache.counts_dirty = false; return SNN_OK; }
     {
         // live transmitter types: slots of the specialised input pass; planes of dead types must read as zero
         uint32_t mask = 0;
         for (const auto &kv : net->lattice_nt_mask) mask |= kv.second;
-        if (mask != net->live_mask_applied) {
-            net->n_live = 0;
+        if (mask != net->cache.live_mask_applied) {
+            net->cache.n_live = 0;
             for (uint32_t k = 0; k < K_TYPES; ++k)
-                if (mask >> k & 1u) net->live_type[net->n_live++] = k;
-            for (uint32_t s = net->n_live, k = 0; s < K_TYPES; ++k)          // unused slots: the remaining types
-                if (!(mask >> k & 1u)) net->live_type[s++] = k;
-            if (net->n_live == 0) net->n_live = 1;                            // nothing released: slot 0 sums zeros
+                if (mask >> k & 1u) net->cache.live_type[net->cache.n_live++] = k;
+            for (uint32_t s = net->cache.n_live, k = 0; s < K_TYPES; ++k)          // unused slots: the remaining types
+                if (!(mask >> k & 1u)) net->cache.live_type[s++] = k;
+            if (net->cache.n_live == 0) net->cache.n_live = 1;                            // nothing released: slot 0 sums zeros
             HIP_TRY(hipMemsetAsync(net->part_t, 0, (size_t)K_TYPES * net->n_chunks * net->ld * 4, net->stream),
                     SNN_ERR_BUFFER_WRITE);
-            net->live_mask_applied = mask;
+            net->cache.live_mask_applied = mask;
         }
     }
     HIP_TRY(hipMemsetAsync(net->n_in, 0, (size_t)net->ld * 4, net->stream), SNN_ERR_BUFFER_WRITE);
@@ -1369,7 +1374,7 @@ int ensure_counts(snn_network *net)
         hipLaunchKernelGGL(k_graph_count, grid, dim3(256), 0, net->stream, a);
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
     }
-    net->counts_dirty = false;
+    net->cache.counts_dirty = false;
     return SNN_OK;
 }
 

@@ -49,12 +49,12 @@ uint32_t spike_train_args(snn_network *net, SpikeTrainArgs &a, int iterate, long
     a.iterate = iterate; a.lattice_clock = net->st_clock_dev; a.step_offset = step_offset;
     a.has_nt = net->any_nt_cells ? 1 : 0;
     a.view_clock = view_clock;
-    a.vhist_row = (iterate && record_now(net) && net->want_vhist && net->st_vhist) ? net->st_vhist + (size_t)net->hist_steps * net->c_pad : nullptr;
+    a.vhist_row = (iterate && record_now(net) && net->want_vhist && net->st_vhist) ? net->st_vhist + (size_t)net->cur.hist_steps * net->c_pad : nullptr;
     a.cell_list = net->cell_list_dev; a.n_listed = net->n_cells_listed;
     const uint32_t work = net->cell_list_dev ? net->n_cells_listed : net->nc;
     if (work && net->cell_view[0]) {
-        if (iterate) net->cell_view_cur ^= 1;
-        a.view_out = net->cell_view[net->cell_view_cur];
+        if (iterate) net->cache.cell_view_cur ^= 1;
+        a.view_out = net->cell_view[net->cache.cell_view_cur];
     }
     return work;
 }
@@ -85,7 +85,7 @@ inline bool matrix_streamed(const snn_network *net)
 bool stdp_deferral_applies(const snn_network *net)
 {
     if (SNN_HAVE_CUSTOM_MODEL) return false;      // a library carrying generated code keeps the standalone kernels (shorter compile)
-    if (!net->defer_stdp || !net->any_plasticity || net->any_modulation || net->any_whist || !matrix_streamed(net) || net->any_conn_kind ||
+    if (!net->opt.defer_stdp || !net->any_plasticity || net->any_modulation || net->any_whist || !matrix_streamed(net) || net->any_conn_kind ||
         net->lattices.size() > (size_t)STDP_MAX_LATTICES || net->n_loc == 0)
         return false;
     for (size_t l = 0; l < net->lattices.size(); ++l)
@@ -104,7 +104,7 @@ StdpArgs stdp_args(snn_network *net)
     a.spike_list = net->spike_list; a.spike_count = net->spike_count;
     a.flag = nullptr; a.dcol = net->stdp_dcol; a.drow = net->stdp_drow;
     a.dcol_stride = net->dcol_stride; a.n_lattices = (uint32_t)net->lattices.size();
-    a.clock = net->clock;
+    a.clock = net->cur.clock;
     a.conn_kind = net->any_conn_kind ? net->conn_kind_dev.get() : nullptr;
     a.st_lattice_slot = net->ca.lattice_slot;
     return a;
@@ -132,7 +132,7 @@ int launch_inputs_dense(snn_network *net, InputsPart part, InputsArgs &a, uint32
     // same-box A/B of the two streamed shapes (profiles/ab_input_shape.py, profiles/r03/ab_input_shape_by_size.txt): the
     // 2-column shape wins by 0.8 - 2.4 % from 96x96 to 240x240 (waves4 up to 50 625), the 4-column shape by 0.5 % at 256x256
     int shape = resident ? 0 : (waves4 < 57600 ? 2 : 1);
-    if (net->force_shape > 0 && !resident) shape = net->force_shape;     // SNN_AMD_INPUT_SHAPE=1|2 (experiments)
+    if (net->opt.input_shape > 0 && !resident) shape = net->opt.input_shape;     // SNN_AMD_INPUT_SHAPE=1|2 (experiments)
     if (net->rstdp_pending && part != INPUTS_ALL) TRY(flush_rstdp(net));
     const bool stdp_fused = !LEAN_INPUT_PASS && net->stdp_pending && !net->rstdp_pending && part == INPUTS_ALL && shape != 0;
     if (net->stdp_pending && !stdp_fused) TRY(flush_stdp(net));
@@ -184,7 +184,7 @@ int launch_inputs_dense(snn_network *net, InputsPart part, InputsArgs &a, uint32
                 in_shape(SH, [&](dim3 grid, dim3 block) {
                     auto pass = [&](auto NT) { hipLaunchKernelGGL((k_inputs_dense<E(), C(), SH(), NT()>), grid, block, 0, net->stream, a); };
                     if constexpr (!C() || LEAN_INPUT_PASS) pass(int_c<3>{});
-                    else for_value<1, 2, 3>((int)net->n_live, pass);
+                    else for_value<1, 2, 3>((int)net->cache.n_live, pass);
                 });
             });
         });
@@ -206,11 +206,11 @@ int launch_inputs(snn_network *net, InputsPart part = INPUTS_ALL)
     a.W = net->W; a.ld = net->ld; a.n_loc = net->n_loc; a.q0 = net->q0; a.rows = net->rowmap; a.n_neurons = net->nn; a.n_tot = net->n_tot;
     a.xbuf = net->xbuf; a.xl = net->xl; a.gap_conductance = net->na.gap_conductance; a.uni = net->uni_neuron;
     a.st_value = net->ca.presyn_value; a.st_last_firing_time = net->ca.last_firing_time;
-    a.st_view = net->cell_view[net->cell_view_cur];
+    a.st_view = net->cell_view[net->cache.cell_view_cur];
     a.st_nt_t = net->ca.nt_t; a.st_nt_flags = net->ca.nt_flags; a.c_pad = net->c_pad;
     a.nt_flags = net->na.nt_flags; a.n_pad = net->n_pad;
     a.part_i = net->part_i; a.part_t = net->part_t; a.n_chunks = net->n_chunks;
-    for (int k = 0; k < K_TYPES; ++k) a.live_type[k] = net->live_type[k];
+    for (int k = 0; k < K_TYPES; ++k) a.live_type[k] = net->cache.live_type[k];
     // LOCAL + REMOTE = one pass over W (counted on the REMOTE half; a lone shard has no REMOTE half)
     hipEvent_t e1 = nullptr;
     TRY(profile_open(net, PROFILE_GRAPH_PASS, (part == INPUTS_LOCAL && lc_count < net->n_chunks) ? 0 : 1, &e1));
@@ -239,32 +239,32 @@ int launch_update(snn_network *net)
     a.n = net->na;
     a.part_i = net->part_i; a.part_t = net->part_t; a.n_in = net->n_in; a.tcount = net->tcount;
     a.ld = net->ld; a.n_chunks = net->n_tot ? net->n_chunks : 0; a.q0 = net->q0; a.n_loc = net->n_loc; a.rows = net->rowmap;
-    a.clock = net->clock;
+    a.clock = net->cur.clock;
     a.electrical = net->electrical; a.chemical = net->chemical; a.nt_kind = net->nt_kind; a.rc_kind = net->rc_kind;
-    a.vhist_row = (record_now(net) && net->want_vhist && net->vhist) ? net->vhist + (size_t)net->hist_steps * net->n_pad : nullptr;
-    a.spike_row = (record_now(net) && net->want_raster && net->raster) ? net->raster + (size_t)net->hist_steps * (net->n_pad / 64) : nullptr;
+    a.vhist_row = (record_now(net) && net->want_vhist && net->vhist) ? net->vhist + (size_t)net->cur.hist_steps * net->n_pad : nullptr;
+    a.spike_row = (record_now(net) && net->want_raster && net->raster) ? net->raster + (size_t)net->cur.hist_steps * (net->n_pad / 64) : nullptr;
     a.spike_counts = net->want_counts ? net->spike_counts : nullptr;
     a.xout = net->xbuf; a.xout2 = nullptr;
     a.has_nt = net->any_nt_neurons ? 1 : 0;
-    a.live_mask = net->live_mask_applied;       // transmitter types some neuron or cell releases (ensure_counts; all ones: unknown)
+    a.live_mask = net->cache.live_mask_applied;       // transmitter types some neuron or cell releases (ensure_counts; all ones: unknown)
     a.bcm = net->model == SNN_MODEL_BCM_IZHIKEVICH;
     a.model_is_custom = net->model == SNN_MODEL_CUSTOM;
     // dense shard handles: the own slot of the all-gather buffer is written by this launch (no pack launch)
     net->update_packed = false;
-    if (net->sharded && !net->csr && net->update_packs && !net->x_dirty && net->x_mode == SNN_EXCHANGE_ALLGATHER &&
+    if (net->sharded && !net->csr && net->opt.update_packs && !net->x_dirty && net->x_mode == SNN_EXCHANGE_ALLGATHER &&
         net->wire && net->x_block_words && net->n_loc <= net->shard_stride) {
         a.wire_out = net->wire + (size_t)net->shard_index * net->x_block_words;
         a.wire_count = net->shard_stride; a.wire_planes = net->x_planes;
         for (uint32_t s = 0; s < net->x_planes; ++s) a.wire_plane_id[s] = net->x_plane_id[s];
         net->update_packed = true;
     }
-    net->shadow_valid = false;            // the exchange buffer moves on without the shadows
+    net->cache.shadow_valid = false;            // the exchange buffer moves on without the shadows
     const uint32_t ub = 256u;          // (one wavefront per workgroup for small launches was measured: no gain)
     dim3 grid((net->ld + ub - 1) / ub);
     // built-in models on dense handles with chemical synapses: the partials of every plane requested together
-    const bool all_planes = net->update_all_planes && net->chemical && !net->csr && net->model != SNN_MODEL_CUSTOM;
+    const bool all_planes = net->opt.update_all_planes && net->chemical && !net->csr && net->model != SNN_MODEL_CUSTOM;
     // ... and, by default, WIDE: four wavefronts share a column's partials and three of them warm the cache for the fourth
-    const bool wide = all_planes && net->update_all_planes >= 2 && a.n_chunks >= 4 && (a.n_chunks + 3) / 4 <= 32;
+    const bool wide = all_planes && net->opt.update_all_planes >= 2 && a.n_chunks >= 4 && (a.n_chunks + 3) / 4 <= 32;
     TouchList touch{};
     if (wide) {
         grid = dim3(net->ld / 64);
@@ -283,7 +283,7 @@ int launch_update(snn_network *net)
         for (int k = 0; k < K_TYPES; ++k) if (a.live_mask >> k & 1u) add(net->xbuf + net->xl.at(0, PLANE_T0 + k));
         touch.by_column[touch.n_column++] = net->n_in;
         for (int k = 0; k < K_TYPES; ++k) if (a.live_mask >> k & 1u) touch.by_column[touch.n_column++] = net->tcount + (size_t)k * net->ld;
-        if (net->update_all_planes == 3) touch.n_neuron = touch.n_column = 0;      // (A/B: the wide form without the cache warming)
+        if (net->opt.update_all_planes == 3) touch.n_neuron = touch.n_column = 0;      // (A/B: the wide form without the cache warming)
     }
     for_model(UpdateModels{}, net->model, [&](auto M) {
         if constexpr (M() == CUSTOM_MODEL) hipLaunchKernelGGL((k_update<M(), false>), grid, dim3(ub), 0, net->stream, a);
@@ -310,7 +310,7 @@ int launch_plasticity(snn_network *net)
 // small dense unsharded networks under STDP (no BCM lattice among the plastic ones): compaction and both scatters in one launch
 bool stdp_small_applies(const snn_network *net)
 {
-    if (!net->stdp_small || net->csr || net->sharded || net->n_tot > 1024u || net->n_loc != net->nn || net->nn == 0) return false;
+    if (!net->opt.stdp_small || net->csr || net->sharded || net->n_tot > 1024u || net->n_loc != net->nn || net->nn == 0) return false;
     // ANY lattice under the BCM rule rules the form out, plastic or not (as in stdp_deferral_applies): k_stdp_small visits the
     // outgoing edge j -> r under the rule of r's lattice with zero activities, which is not what k_stdp_rows computes for a BCM
     // lattice whose own do_plasticity is off but which receives edges from a plastic STDP lattice
@@ -333,7 +333,7 @@ int launch_plasticity_kernels(snn_network *net)
     hipLaunchKernelGGL(k_spike_compact, dim3((net->nn + 255) / 256), dim3(256), 0, net->stream, a);
     HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
     if (net->n_loc == 0) return SNN_OK;
-    if (defer && net->defer_stdp == 3) {
+    if (defer && net->opt.defer_stdp == 3) {
         // the incoming edges now (the column scatter), the outgoing edges with the next input pass: the row half costs that pass
         // no fetch and only full-line stores, where k_stdp_rows reads and writes back every line of the listed rows
         hipLaunchKernelGGL(k_stdp_columns, dim3((net->n_tot + 255) / 256, 64), dim3(256), 0, net->stream, a);
@@ -350,7 +350,7 @@ int launch_plasticity_kernels(snn_network *net)
         hipLaunchKernelGGL(k_stdp_prepare, dim3((std::max(net->n_tot, net->n_loc) + 255) / 256), dim3(256), 0, net->stream, a);
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
         net->stdp_pending = true;
-        if (net->defer_stdp == 2) TRY(flush_stdp(net));      // the prepared deltas applied right away by the scatter passes
+        if (net->opt.defer_stdp == 2) TRY(flush_stdp(net));      // the prepared deltas applied right away by the scatter passes
         return SNN_OK;
     }
     if (net->csr) {
@@ -366,7 +366,7 @@ int launch_plasticity_kernels(snn_network *net)
         return SNN_OK;
     }
     const unsigned sy = 64;   // spiking neurons processed concurrently; the rest grid-strides
-    if (net->stdp_columns_form == 1) {
+    if (net->opt.stdp_columns_form == 1) {
         // quad form: 256 listed columns per workgroup (64 per wavefront) x slabs of row groups
         const uint32_t groups = (net->n_tot + 3u) / 4u;
         const unsigned slabs = std::max(1u, std::min(1024u, groups / 16u));
@@ -385,7 +385,7 @@ bool fused_step_possible(const snn_network *net)
 {
     // (a library carrying generated code has the one-launch step for ITS neuron model only: shorter compile)
     const bool compiled = !SNN_HAVE_CUSTOM_MODEL || (SNN_HAVE_CUSTOM_NEURON && net->model == SNN_MODEL_CUSTOM);
-    return compiled && net->fused_step && !net->csr && !net->sharded && !net->drive_threshold && net->n_loc && net->n_tot &&
+    return compiled && net->opt.fused_step && !net->csr && !net->sharded && !net->drive_threshold && net->n_loc && net->n_tot &&
            net->n_chunks <= RESIDENT_MAX_CHUNKS && (size_t)net->n_tot * net->ld * 4 <= ((size_t)64 << 20);
 }
 
@@ -484,7 +484,7 @@ int check_reward_cross(snn_network *net)
 int launch_reward_modulation(snn_network *net)
 {
     if (!net->any_modulation || net->nn == 0 || net->n_loc == 0 || !net->trace) return SNN_OK;
-    if (!net->csr && net->defer_rstdp && !net->any_whist && !fused_step_possible(net)) {
+    if (!net->csr && net->opt.defer_rstdp && !net->any_whist && !fused_step_possible(net)) {
         net->rstdp_pending = true;
         net->reward_since_defer = false;
         return SNN_OK;
@@ -601,28 +601,28 @@ int fused_step_args(snn_network *net, InputsArgs &a, UpdateArgs &u, bool in_plac
 {
     const size_t xelems = (size_t)NUM_PLANES * net->xl.stride;
     if (in_place) {
-        net->shadow_valid = false;
+        net->cache.shadow_valid = false;
     } else if (!net->shadow[0]) {
         TRY(dev_alloc_t(net, &net->shadow[0], xelems));
         TRY(dev_alloc_t(net, &net->shadow[1], xelems));
-        net->shadow_valid = false;
+        net->cache.shadow_valid = false;
     }
-    if (!in_place && !net->shadow_valid) {
+    if (!in_place && !net->cache.shadow_valid) {
         // both shadows: entries the step never rewrites (absent transmitter types, padding) must agree everywhere
         for (int i = 0; i < 2; ++i)
             HIP_TRY(hipMemcpyAsync(net->shadow[i], net->xbuf, xelems * 4, hipMemcpyDeviceToDevice, net->stream),
                     SNN_ERR_BUFFER_WRITE);
-        net->shadow_valid = true;
-        net->stat_shadow_refreshes += 1;
+        net->cache.shadow_valid = true;
+        net->stat.shadow_refreshes += 1;
     }
-    float *cur = in_place ? net->xbuf : net->shadow[net->shadow_cur];
-    float *next = in_place ? nullptr : net->shadow[net->shadow_cur ^ 1];
+    float *cur = in_place ? net->xbuf : net->shadow[net->cache.shadow_cur];
+    float *next = in_place ? nullptr : net->shadow[net->cache.shadow_cur ^ 1];
     a = InputsArgs{};
     a.chunk_first = 0; a.hole_begin = net->n_chunks; a.hole_count = 0;
     a.W = net->W; a.ld = net->ld; a.n_loc = net->n_loc; a.q0 = net->q0; a.rows = net->rowmap; a.n_neurons = net->nn; a.n_tot = net->n_tot;
     a.xbuf = cur; a.xl = net->xl; a.gap_conductance = net->na.gap_conductance; a.uni = net->uni_neuron;
     a.st_value = net->ca.presyn_value; a.st_last_firing_time = net->ca.last_firing_time;
-    a.st_view = net->cell_view[net->cell_view_cur];
+    a.st_view = net->cell_view[net->cache.cell_view_cur];
     a.st_nt_t = net->ca.nt_t; a.st_nt_flags = net->ca.nt_flags; a.c_pad = net->c_pad;
     a.nt_flags = net->na.nt_flags; a.n_pad = net->n_pad;
     a.part_i = net->part_i; a.part_t = net->part_t; a.n_chunks = net->n_chunks;
@@ -632,14 +632,14 @@ int fused_step_args(snn_network *net, InputsArgs &a, UpdateArgs &u, bool in_plac
     u.n.xbuf = cur;
     u.part_i = net->part_i; u.part_t = net->part_t; u.n_in = net->n_in; u.tcount = net->tcount;
     u.ld = net->ld; u.n_chunks = net->n_chunks; u.q0 = net->q0; u.n_loc = net->n_loc; u.rows = net->rowmap;
-    u.clock = net->clock;
+    u.clock = net->cur.clock;
     u.electrical = net->electrical; u.chemical = net->chemical; u.nt_kind = net->nt_kind; u.rc_kind = net->rc_kind;
-    u.vhist_row = (record_now(net) && net->want_vhist && net->vhist) ? net->vhist + (size_t)net->hist_steps * net->n_pad : nullptr;
-    u.spike_row = (record_now(net) && net->want_raster && net->raster) ? net->raster + (size_t)net->hist_steps * (net->n_pad / 64) : nullptr;
+    u.vhist_row = (record_now(net) && net->want_vhist && net->vhist) ? net->vhist + (size_t)net->cur.hist_steps * net->n_pad : nullptr;
+    u.spike_row = (record_now(net) && net->want_raster && net->raster) ? net->raster + (size_t)net->cur.hist_steps * (net->n_pad / 64) : nullptr;
     u.spike_counts = net->want_counts ? net->spike_counts : nullptr;
     u.xout = net->xbuf; u.xout2 = next;
     u.has_nt = net->any_nt_neurons ? 1 : 0;
-    u.live_mask = net->live_mask_applied;
+    u.live_mask = net->cache.live_mask_applied;
     u.bcm = net->model == SNN_MODEL_BCM_IZHIKEVICH;
     u.model_is_custom = net->model == SNN_MODEL_CUSTOM;
     return SNN_OK;
@@ -653,7 +653,7 @@ int launch_step_resident(snn_network *net)
     TRY(profile_open(net, PROFILE_GRAPH_PASS, 1, &e1));
     // a chunk's rows over four wavefronts (k_step_resident_q) where the workgroup stays within 512 threads: at most two chunks
     // (a network of at most 64 rows has one quarter's worth of them: nothing to spread, and the turns cost 1 - 8 us)
-    const bool quarters = net->resident_quarters && net->n_chunks <= 2 && net->n_tot > 64;
+    const bool quarters = net->opt.resident_quarters && net->n_chunks <= 2 && net->n_tot > 64;
     const dim3 grid((net->n_loc + 63) / 64), block(64 * net->n_chunks * (quarters ? 4 : 1));
     for_model(ResidentStepModels{}, net->model, [&](auto M) {
         for_synapses(net->electrical, net->chemical, [&](auto E, auto C) {
@@ -663,7 +663,7 @@ int launch_step_resident(snn_network *net)
     });
     HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
     TRY(profile_close(net, e1));
-    net->shadow_cur ^= 1;
+    net->cache.shadow_cur ^= 1;
     return SNN_OK;
 }
 
@@ -671,9 +671,9 @@ int launch_step_resident(snn_network *net)
 // update to carry, no drive kernel in front, gap junctions on (the chemical-only pass keeps its two kernels).
 bool dense_close_applies(const snn_network *net)
 {
-    return !SNN_HAVE_CUSTOM_MODEL && net->dense_close && !net->csr && !net->sharded && !net->drive_threshold && net->n_loc && net->n_tot &&
+    return !SNN_HAVE_CUSTOM_MODEL && net->opt.dense_close && !net->csr && !net->sharded && !net->drive_threshold && net->n_loc && net->n_tot &&
            net->n_loc == net->nn && net->electrical && matrix_streamed(net) && !net->local_inputs_done && !net->stdp_pending &&
-           !net->rstdp_pending && net->force_shape == 0 && net->n_chunks <= net->dense_close_max_chunks;
+           !net->rstdp_pending && net->opt.input_shape == 0 && net->n_chunks <= net->opt.dense_close_max_chunks;
 }
 
 int launch_dense_close(snn_network *net)
@@ -693,8 +693,8 @@ int launch_dense_close(snn_network *net)
     }
     r.tile_done = net->tile_done;
     // one live transmitter type: the pass specialised on it (the planes of the other types hold zeros, which the update adds)
-    const bool one_type = net->chemical && net->n_live == 1;
-    if (one_type) for (int k = 0; k < K_TYPES; ++k) r.in.live_type[k] = net->live_type[k];
+    const bool one_type = net->chemical && net->cache.n_live == 1;
+    if (one_type) for (int k = 0; k < K_TYPES; ++k) r.in.live_type[k] = net->cache.live_type[k];
     hipEvent_t e1 = nullptr;
     TRY(profile_open(net, PROFILE_GRAPH_PASS, 1, &e1));
     const dim3 grid(tiles, net->n_chunks), block(256);
@@ -707,7 +707,7 @@ int launch_dense_close(snn_network *net)
     });
     HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
     TRY(profile_close(net, e1));
-    net->shadow_cur ^= 1;
+    net->cache.shadow_cur ^= 1;
     return SNN_OK;
 }
 
@@ -727,7 +727,7 @@ bool run_resident_applies(const snn_network *net)
 // connection kinds of a reward-modulated network, the scatter form of the weight update (defer_stdp 0)
 bool run_resident_stdp_ok(const snn_network *net)
 {
-    if (!net->persistent_stdp || net->chemical || net->nc || net->n_tot > RUN_RESIDENT_GROUP_ROWS || net->any_conn_kind || net->defer_stdp ||
+    if (!net->opt.persistent_stdp || net->chemical || net->nc || net->n_tot > RUN_RESIDENT_GROUP_ROWS || net->any_conn_kind || net->opt.defer_stdp ||
         net->lattices.size() > RUN_STDP_MAX_LATTICES)
         return false;
     for (size_t l = 0; l < net->lattices.size(); ++l)
@@ -736,10 +736,10 @@ bool run_resident_stdp_ok(const snn_network *net)
 }
 bool run_resident_shape(const snn_network *net)
 {
-    const bool chem_ok = !net->chemical || (net->n_tot <= RUN_RESIDENT_GROUP_ROWS && net->persistent_chem &&
+    const bool chem_ok = !net->chemical || (net->n_tot <= RUN_RESIDENT_GROUP_ROWS && net->opt.persistent_chem &&
                                             net->nt_kind != SNN_NT_CUSTOM && net->rc_kind != SNN_RC_CUSTOM);
-    return !SNN_HAVE_CUSTOM_MODEL && net->fused_step && !net->csr && !net->sharded && !net->drive_threshold && net->n_loc &&
-           net->persistent_run && net->n_loc == net->nn && net->nn + net->nc == net->n_tot &&
+    return !SNN_HAVE_CUSTOM_MODEL && net->opt.fused_step && !net->csr && !net->sharded && !net->drive_threshold && net->n_loc &&
+           net->opt.persistent_run && net->n_loc == net->nn && net->nn + net->nc == net->n_tot &&
            (net->nc == 0 || ((net->st_kind == SNN_ST_POISSON || net->st_kind == SNN_ST_RATE) && !net->any_nt_cells &&
                              !net->cell_list_dev && !SNN_HAVE_CUSTOM_REFRACTORINESS)) &&
            net->n_tot <= RUN_RESIDENT_MAX_NEURONS && (net->electrical || net->chemical) && chem_ok &&
@@ -836,7 +836,7 @@ int launch_run_resident(snn_network *net, uint64_t iterations, uint64_t steps_be
         HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
         if (net->run_failed[1]) {
             net->run_failed[1] = 0u;
-            net->persistent_run = 0;                 // one launch per step for this handle from now on
+            net->opt.persistent_run = 0;                 // one launch per step for this handle from now on
             return SNN_OK;
         }
         net->run_probed_grid = n_groups;
@@ -860,22 +860,22 @@ int launch_run_resident(snn_network *net, uint64_t iterations, uint64_t steps_be
         r.n_groups = row_groups;
         r.tag_base = net->run_tag;
         r.failed = net->run_failed;
-        r.spin_limit = net->run_spin_limit;
+        r.spin_limit = net->opt.run_resident_spin_limit;
         // (the test hook counts steps of the RUN CALL: a fault can be placed in a later chunk of it)
-        r.fault_step = (net->run_fault_step > steps_before && net->run_fault_step <= steps_before + steps) ? (uint32_t)(net->run_fault_step - steps_before) : 0u;
+        r.fault_step = (net->opt.run_resident_fault_step > steps_before && net->opt.run_resident_fault_step <= steps_before + steps) ? (uint32_t)(net->opt.run_resident_fault_step - steps_before) : 0u;
         r.cells = net->ca;
         r.st_kind = net->st_kind;
         r.lattice_clock = net->st_clock_dev;
-        r.step_offset0 = net->run_step_offset;
-        r.view_clock0 = net->clock;
-        r.st_vhist_row = (recording(net) && net->want_vhist && net->st_vhist) ? net->st_vhist + (size_t)net->hist_steps * net->c_pad : nullptr;
+        r.step_offset0 = net->cur.run_step_offset;
+        r.view_clock0 = net->cur.clock;
+        r.st_vhist_row = (recording(net) && net->want_vhist && net->st_vhist) ? net->st_vhist + (size_t)net->cur.hist_steps * net->c_pad : nullptr;
         r.st_vhist_stride = net->c_pad;
-        if (!net->run_timing && (net->run_timing_opt || getenv("SNN_AMD_RUN_TIMING"))) TRY(dev_alloc_t(net, &net->run_timing, (size_t)RUN_RESIDENT_MAX_TILES * RUN_RESIDENT_MAX_GROUPS * 4, /*scratch=*/true));
+        if (!net->run_timing && (net->opt.run_timing || getenv("SNN_AMD_RUN_TIMING"))) TRY(dev_alloc_t(net, &net->run_timing, (size_t)RUN_RESIDENT_MAX_TILES * RUN_RESIDENT_MAX_GROUPS * 4, /*scratch=*/true));
         r.timing = net->run_timing;
         // chemical synapses: the transmitter types some NEURON releases travel (cells with transmitters keep the per-step forms)
         if (net->chemical)
             for (uint32_t k = 0; k < K_TYPES; ++k)
-                if (net->live_mask_applied != 0xFFFFFFFFu && (net->live_mask_applied >> k & 1u)) r.live_type[r.n_live++] = k;
+                if (net->cache.live_mask_applied != 0xFFFFFFFFu && (net->cache.live_mask_applied >> k & 1u)) r.live_type[r.n_live++] = k;
         const bool stdp = net->any_plasticity;                  // (run_resident_shape let it through: run_resident_stdp_ok)
         if (stdp) {
             if (!net->run_w_out) TRY(dev_alloc_t(net, &net->run_w_out, wcount(net->n_tot, net->ld)));
@@ -931,17 +931,17 @@ int launch_run_resident(snn_network *net, uint64_t iterations, uint64_t steps_be
             if (net->run_failed[0]) return SNN_OK;
             HIP_TRY(hipMemcpyAsync(net->W, net->run_w_out, (size_t)4 * ((net->n_tot + 3) / 4) * net->ld * 4, hipMemcpyDeviceToDevice, net->stream),
                     SNN_ERR_BUFFER_WRITE);
-            net->clock += steps - 1;
+            net->cur.clock += steps - 1;
             TRY(launch_plasticity(net));
-            net->clock -= steps - 1;
-            net->stat_run_stdp_steps += steps;
+            net->cur.clock -= steps - 1;
+            net->stat.run.stdp_steps += steps;
         }
         net->run_tag += steps;
-        net->stat_run_launches += 1;
-        net->stat_run_steps += steps;
-        net->clock += steps;
-        net->run_step_offset += steps;
-        if (recording(net)) { net->hist_steps += steps; net->hist_tick += steps; }
+        net->stat.run.launches += 1;
+        net->stat.run.steps += steps;
+        net->cur.clock += steps;
+        net->cur.run_step_offset += steps;
+        if (recording(net)) { net->cur.hist_steps += steps; net->cur.hist_tick += steps; }
     }
     return SNN_OK;
 }
@@ -950,7 +950,7 @@ int launch_run_resident(snn_network *net, uint64_t iterations, uint64_t steps_be
 // is written into the shadow the next step reads as well (wire_args / k_step_close).
 bool fused_csr_step_applies(const snn_network *net)
 {
-    return !SNN_HAVE_CUSTOM_MODEL && net->fused_step && net->csr && net->csr_ptr && !net->drive_threshold &&
+    return !SNN_HAVE_CUSTOM_MODEL && net->opt.fused_step && net->csr && net->csr_ptr && !net->drive_threshold &&
            net->n_loc && !net->local_inputs_done &&
            (!net->sharded || net->n_shards == 1 || net->x_mode == SNN_EXCHANGE_HALO);
 }
@@ -970,7 +970,7 @@ bool csr_fast_step(const snn_network *net)
 bool cells_ride_allowed(const snn_network *net)         // (before the first run the two-copy view is not allocated yet)
 {
     return net->nc && net->electrical && !net->chemical && !net->any_plasticity && !net->any_modulation &&
-           net->cells_in_step && (!net->sharded || net->n_shards == 1 || csr_fast_step(net));
+           net->opt.cells_in_step && (!net->sharded || net->n_shards == 1 || csr_fast_step(net));
 }
 bool cells_ride_with_rows(const snn_network *net) { return net->cell_view[0] && cells_ride_allowed(net); }
 
@@ -995,7 +995,7 @@ int launch_step_csr(snn_network *net, CsrStepPart part = CSR_STEP_ALL, bool pack
     if (net->peer_run) {         // ... which the peers stored as granules into this handle's set of the previous step's parity
         c.c.g.halo64 = net->p2p_recv[(net->p2p_epoch + 1u) & 1u];
         c.c.g.halo_tag = net->p2p_epoch;
-        c.c.g.spin_limit = net->p2p_spin_limit;
+        c.c.g.spin_limit = net->opt.halo_peer_spin_limit;
         c.c.g.failed = PeerFailure{{net->p2p_failed, net->p2p_done_blocks + 1}};
         // a halo neuron's granules are adjacent, one per plane of the plan, in the plan's order
         c.c.g.halo_slot_v = 0xFFFFFFFFu;
@@ -1004,7 +1004,7 @@ int launch_step_csr(snn_network *net, CsrStepPart part = CSR_STEP_ALL, bool pack
             if (net->x_plane_id[s] == (uint32_t)PLANE_V) c.c.g.halo_slot_v = s;
             else c.c.g.halo_slot_t[net->x_plane_id[s] - PLANE_T0] = s;
         }
-        c.c.g.delay = net->peer_delay; c.c.g.delay_seed = net->shard_index * 7919u + 1u;
+        c.c.g.delay = net->opt.halo_peer_delay; c.c.g.delay_seed = net->shard_index * 7919u + 1u;
     }
     if (pack) {
         c.pack.ptr = net->pack_ptr_dev; c.pack.seg_off = net->pack_segoff_dev; c.pack.seg_count = net->pack_count_dev;
@@ -1017,20 +1017,20 @@ int launch_step_csr(snn_network *net, CsrStepPart part = CSR_STEP_ALL, bool pack
             c.pack.flags = net->p2p_flags;
             // the set was last read by the peer's step of epoch - 1 (rows and mirror job): its counter says when that is over
             c.pack.tag_out = net->p2p_epoch + 1u; c.pack.need_done = net->p2p_epoch - 1u;
-            c.pack.spin_limit = net->p2p_spin_limit; c.pack.failed = PeerFailure{{net->p2p_failed, net->p2p_done_blocks + 1}};
+            c.pack.spin_limit = net->opt.halo_peer_spin_limit; c.pack.failed = PeerFailure{{net->p2p_failed, net->p2p_done_blocks + 1}};
             c.pack.nt_flags = net->na.nt_flags; c.pack.n_pad = net->n_pad;
-            c.pack.delay = net->peer_delay; c.pack.delay_seed = net->shard_index * 7919u + 2u;
+            c.pack.delay = net->opt.halo_peer_delay; c.pack.delay_seed = net->shard_index * 7919u + 2u;
         }
     }
     if (net->peer_run) {
         c.peer.signal = net->p2p_signal_dev; c.peer.n_signal = net->p2p_n_signal;
         c.peer.done_value = net->p2p_epoch - 1u;     // this launch running = the step of the epoch before is over
-        c.peer.delay = net->peer_delay; c.peer.delay_seed = net->shard_index * 7919u + 3u;
+        c.peer.delay = net->opt.halo_peer_delay; c.peer.delay_seed = net->shard_index * 7919u + 3u;
     }
     // the cells ride with the step's last row launch (the rows of BOTH launches read the view the cells do not write)
     const bool last_part = part != CSR_STEP_BORDER || net->n_interior == 0;
     if (last_part && !net->cells_stepped && cells_ride_with_rows(net)) {
-        c.tail.cell_blocks = (spike_train_args(net, c.tail.cells, 1, net->run_step_offset, net->clock + 1) + 255) / 256;
+        c.tail.cell_blocks = (spike_train_args(net, c.tail.cells, 1, net->cur.run_step_offset, net->cur.clock + 1) + 255) / 256;
         net->cells_stepped = true;
     }
     if (last_part && net->direct_run && !net->tail_done) {
@@ -1039,14 +1039,14 @@ int launch_step_csr(snn_network *net, CsrStepPart part = CSR_STEP_ALL, bool pack
         // the outgoing set the NEXT step packs into (its last send completed before this step's first launch)
         if (net->stamp_pending && net->seg_n[1] && net->recv_total) {
             c.tail.recv = wire_args(net, 1, net->hx_par ^ 1);
-            c.tail.recv.clock = net->clock - 1;
+            c.tail.recv.clock = net->cur.clock - 1;
             c.tail.recv.xbuf2 = nullptr;
             c.tail.recv_total = net->recv_total;
             c.tail.recv_segments = net->seg_n[1];
             c.tail.unpack_blocks = (net->recv_total + 255) / 256;
             if (net->peer_run) {         // the same set the rows of this launch read
                 c.tail.recv64 = net->p2p_recv[(net->p2p_epoch + 1u) & 1u]; c.tail.recv_tag = net->p2p_epoch;
-                c.tail.spin_limit = net->p2p_spin_limit; c.tail.failed = PeerFailure{{net->p2p_failed, net->p2p_done_blocks + 1}};
+                c.tail.spin_limit = net->opt.halo_peer_spin_limit; c.tail.failed = PeerFailure{{net->p2p_failed, net->p2p_done_blocks + 1}};
             }
         }
         net->stamp_pending = false;
@@ -1057,14 +1057,14 @@ int launch_step_csr(snn_network *net, CsrStepPart part = CSR_STEP_ALL, bool pack
         }
     }
     const uint32_t tail_blocks = c.tail.blocks();
-    c.xcd_bands = net->csr_xcd_bands ? 1u : 0u;
+    c.xcd_bands = net->opt.csr_xcd_bands ? 1u : 0u;
     // the step image (static weights, gap junctions only, every source in this handle's own arrays): records of 16 bytes and the
     // slices' presynaptic windows in LDS
     // ... shard handles too: border and interior launches, the border rows packing as they go; in a direct run (the halo gathered
     // from the received segments) the image is the one built with the exchange plan -- a halo neuron's source is its word of the
     // receive buffer.  Not the peer form (a granule is polled, not copied).
     const bool direct_image = net->direct_run && !net->peer_run;
-    const bool image = net->csr_image && !net->peer_run && net->electrical && !net->chemical && !net->any_plasticity && !net->any_modulation &&
+    const bool image = net->opt.csr_image && !net->peer_run && net->electrical && !net->chemical && !net->any_plasticity && !net->any_modulation &&
                        !net->any_conn_kind && net->model != SNN_MODEL_CUSTOM && (net->nc == 0 || c.c.in.st_view) &&
                        (direct_image ? net->csr_img_hdr_direct != nullptr : (net->csr_img_hdr != nullptr && !net->direct_run));
     if (image) {
@@ -1078,7 +1078,7 @@ int launch_step_csr(snn_network *net, CsrStepPart part = CSR_STEP_ALL, bool pack
             stale = false;
         }
         c.img.hdr = hdr; c.img.rec = rec;
-        if (part != CSR_STEP_INTERIOR) net->stat_steps_sparse_image += 1;      // (a step is one ALL launch, or a BORDER launch and perhaps an INTERIOR one)
+        if (part != CSR_STEP_INTERIOR) net->stat.steps_sparse_image += 1;      // (a step is one ALL launch, or a BORDER launch and perhaps an INTERIOR one)
     } else if (net->any_plasticity || net->any_modulation || net->any_conn_kind) {
         net->img_stale = net->img_stale_direct = true;          // this step's weight updates leave the records behind
     }
@@ -1101,7 +1101,7 @@ int launch_step_csr(snn_network *net, CsrStepPart part = CSR_STEP_ALL, bool pack
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
         TRY(profile_close(net, e1));
     }
-    if (part != CSR_STEP_BORDER) net->shadow_cur ^= 1;       // S(t+1) is complete once the last part is enqueued
+    if (part != CSR_STEP_BORDER) net->cache.shadow_cur ^= 1;       // S(t+1) is complete once the last part is enqueued
     return SNN_OK;
 }
 
@@ -1118,21 +1118,21 @@ int step_begin(snn_network *net)
 {
     if (net->drive_threshold && net->nn) {
         hipLaunchKernelGGL(k_synthetic_drive, dim3((net->nn + 255) / 256), dim3(256), 0, net->stream, net->xbuf, net->xl,
-                           net->nn, net->drive_seed, net->clock, net->drive_threshold, net->drive_voltage);
+                           net->nn, net->drive_seed, net->cur.clock, net->drive_threshold, net->drive_voltage);
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
     }
-    if (fused_step_applies(net)) { net->stat_steps_dense_one_launch += 1; return launch_step_resident(net); }
-    if (dense_close_applies(net)) { net->stat_steps_dense_close += 1; return launch_dense_close(net); }
+    if (fused_step_applies(net)) { net->stat.steps_dense_one_launch += 1; return launch_step_resident(net); }
+    if (dense_close_applies(net)) { net->stat.steps_dense_close += 1; return launch_dense_close(net); }
     if (csr_fast_step(net) && net->peer_run) {
         // peer form: nothing to overlap with -- border and interior slices in ONE launch, the border rows store into the peers
-        net->stat_steps_sparse_one_launch += 1;
+        net->stat.steps_sparse_one_launch += 1;
         TRY(launch_step_csr(net, CSR_STEP_ALL, /*pack=*/true));
         net->step_packed = true;
         net->interior_pending = false;
         return SNN_OK;
     }
     if (csr_fast_step(net)) {
-        net->stat_steps_sparse_split += 1;
+        net->stat.steps_sparse_split += 1;
         // border slices first, writing the outgoing segments themselves; the interior slices follow once the caller has
         // started the exchange (step_interior: snn_run_sharded, snn_step_begin_local, or at the latest step_end)
         // (direct runs: the set this step packs into was cleared behind the previous step's rows, or at the run's start)
@@ -1143,8 +1143,8 @@ int step_begin(snn_network *net)
         net->interior_pending = true;
         return SNN_OK;
     }
-    if (fused_csr_step_applies(net)) { net->stat_steps_sparse_one_launch += 1; return launch_step_csr(net); }
-    net->stat_steps_two_kernel += 1;
+    if (fused_csr_step_applies(net)) { net->stat.steps_sparse_one_launch += 1; return launch_step_csr(net); }
+    net->stat.steps_two_kernel += 1;
     TRY(launch_inputs(net, net->local_inputs_done ? INPUTS_REMOTE : INPUTS_ALL));
     net->local_inputs_done = false;
     TRY(launch_update(net));
@@ -1157,7 +1157,7 @@ uint32_t plan_plane_mask(const snn_network *net);
 int step_end(snn_network *net)
 {
     // of the neurons owned elsewhere only what this step's exchange carries stays current in the mirror
-    if (net->sharded && net->n_shards > 1) net->mirror_mask = plan_plane_mask(net);
+    if (net->sharded && net->n_shards > 1) net->cache.mirror_mask = plan_plane_mask(net);
     TRY(step_interior(net));
     if (net->step_packed) {
         // the fast sparse step (csr_fast_step): unpack, spike trains and the clearing of the outgoing bitmaps in ONE launch
@@ -1166,18 +1166,18 @@ int step_end(snn_network *net)
             // nothing to unpack before the next rows: they read the received segments themselves
             if (!net->cells_stepped) TRY(launch_step_close(net, /*cells=*/true, /*unpack=*/false));
             net->stamp_pending = true;
-            net->stat_direct_steps += 1;
+            net->stat.direct_steps += 1;
             net->tail_done = false;
             net->hx_par ^= 1;
-            if (net->peer_run) { net->p2p_epoch += 1; net->stat_peer_steps += 1; }
+            if (net->peer_run) { net->p2p_epoch += 1; net->stat.peer_steps += 1; }
         } else {
             TRY(launch_step_close(net, /*cells=*/!net->cells_stepped, /*unpack=*/true));
         }
         net->cells_stepped = false;
-        net->clock += 1;
-        net->run_step_offset += 1;
-        if (record_now(net)) net->hist_steps += 1;
-        if (recording(net)) net->hist_tick += 1;
+        net->cur.clock += 1;
+        net->cur.run_step_offset += 1;
+        if (record_now(net)) net->cur.hist_steps += 1;
+        if (recording(net)) net->cur.hist_tick += 1;
         return SNN_OK;
     }
     TRY(launch_exchange_unpack(net));      // shard handles: the other ranks' state of this step, their last_firing_time
@@ -1187,7 +1187,7 @@ int step_end(snn_network *net)
         if (!net->any_whist || !record_now(net)) return SNN_OK;
         for (const auto &l : net->lattices) {
             if (net->want_whist[l.slot] != order || l.count == 0) continue;
-            float *dst = net->whist[l.slot] + (size_t)net->hist_steps * l.count * l.count;
+            float *dst = net->whist[l.slot] + (size_t)net->cur.hist_steps * l.count * l.count;
             hipLaunchKernelGGL(k_weight_snapshot, dim3((l.count + 255) / 256, l.count), dim3(256), 0, net->stream,
                                net->W, net->ld, l.first, l.count, dst);
             HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
@@ -1204,25 +1204,25 @@ int step_end(snn_network *net)
         const size_t nl = net->lattices.size();
         SummaryArgs sa{};
         sa.xbuf = net->xbuf; sa.xl = net->xl; sa.first = net->lat_first_dev; sa.count = net->lat_count_dev;
-        sa.avg_row = net->want_avg ? net->summ_avg + (size_t)net->hist_steps * nl : nullptr;
-        sa.eeg_row = net->want_eeg ? net->summ_eeg + (size_t)net->hist_steps * nl : nullptr;
+        sa.avg_row = net->want_avg ? net->summ_avg + (size_t)net->cur.hist_steps * nl : nullptr;
+        sa.eeg_row = net->want_eeg ? net->summ_eeg + (size_t)net->cur.hist_steps * nl : nullptr;
         sa.reference_voltage = net->eeg_ref; sa.distance = net->eeg_dist; sa.conductivity = net->eeg_cond;
         hipLaunchKernelGGL(k_lattice_summary, dim3((unsigned)nl), dim3(256), 0, net->stream, sa);
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
     }
-    net->clock += 1;
-    if (!net->cells_stepped) TRY(launch_spike_trains(net, 1, net->run_step_offset, net->clock));
+    net->cur.clock += 1;
+    if (!net->cells_stepped) TRY(launch_spike_trains(net, 1, net->cur.run_step_offset, net->cur.clock));
     net->cells_stepped = false;
-    net->run_step_offset += 1;
-    if (record_now(net)) net->hist_steps += 1;
-    if (recording(net)) net->hist_tick += 1;
+    net->cur.run_step_offset += 1;
+    if (record_now(net)) net->cur.hist_steps += 1;
+    if (recording(net)) net->cur.hist_tick += 1;
     return SNN_OK;
 }
 
 int grow_history(snn_network *net, uint64_t extra)
 {
     if (!recording(net)) return SNN_OK;
-    const uint64_t need = net->hist_steps + (extra + net->hist_every - 1) / net->hist_every + 1;
+    const uint64_t need = net->cur.hist_steps + (extra + net->hist_every - 1) / net->hist_every + 1;
     if (need <= net->hist_cap && (!net->want_vhist || net->vhist) && (!net->want_raster || net->raster) &&
         (!net->want_avg || net->summ_avg) && (!net->want_eeg || net->summ_eeg)) {
         bool ok = true;
@@ -1234,8 +1234,8 @@ int grow_history(snn_network *net, uint64_t extra)
         if (!wanted || row_bytes == 0) return SNN_OK;
         std::remove_reference_t<decltype(buf)> nb;
         HIP_TRY(snn_malloc(&nb, std::max<size_t>(256, cap * row_bytes)), SNN_ERR_BUFFER_CREATE);
-        if (buf && net->hist_steps)
-            HIP_TRY(hipMemcpyAsync(nb, buf, net->hist_steps * row_bytes, hipMemcpyDeviceToDevice, net->stream),
+        if (buf && net->cur.hist_steps)
+            HIP_TRY(hipMemcpyAsync(nb, buf, net->cur.hist_steps * row_bytes, hipMemcpyDeviceToDevice, net->stream),
                     SNN_ERR_BUFFER_WRITE);
         HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
         buf = std::move(nb);
@@ -1249,7 +1249,7 @@ int grow_history(snn_network *net, uint64_t extra)
     for (const auto &l : net->lattices)
         TRY(regrow(net->whist[l.slot], (size_t)l.count * l.count * 4, net->want_whist[l.slot] != 0));
     net->hist_cap = cap;
-    net->stat_history_regrows += 1;
+    net->stat.history_regrows += 1;
     return SNN_OK;
 }
 
@@ -1269,7 +1269,7 @@ int begin_run(snn_network *net, uint64_t iterations)
     if (net->run_active) return SNN_OK;
     if (net->nc && net->csr && !net->cell_view[0]) {
         for (int i = 0; i < 2; ++i) TRY(dev_alloc_t(net, &net->cell_view[i], (size_t)net->c_pad));
-        net->view_dirty = true;
+        net->cache.view_dirty = true;
     }
     if (net->nc) {
         // from a page-locked staging copy: the transfer may read its source any time until the stream has drained, and the
@@ -1277,11 +1277,11 @@ int begin_run(snn_network *net, uint64_t iterations)
         for (size_t i = 0; i < net->st_clock.size(); ++i) net->st_clock_pinned[i] = net->st_clock[i];
         HIP_TRY(hipMemcpyAsync(net->st_clock_dev, net->st_clock_pinned, net->st_clock.size() * sizeof(long long),
                                hipMemcpyHostToDevice, net->stream), SNN_ERR_BUFFER_WRITE);
-        if (net->view_dirty) { net->stat_view_refreshes += 1; TRY(launch_spike_trains(net, 0, 0, net->clock)); }
+        if (net->cache.view_dirty) { net->stat.view_refreshes += 1; TRY(launch_spike_trains(net, 0, 0, net->cur.clock)); }
     }
-    net->view_dirty = false;
+    net->cache.view_dirty = false;
     TRY(check_reward_cross(net));
-    net->run_step_offset = 0;
+    net->cur.run_step_offset = 0;
     net->run_active = true;
     return SNN_OK;
 }
@@ -1296,8 +1296,8 @@ int end_run(snn_network *net, bool keep_stdp)
     if (!keep_stdp) TRY(flush_stdp(net));
     HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
     if (net->run_active) {
-        for (auto &c : net->st_clock) c += net->run_step_offset;
-        net->run_step_offset = 0;
+        for (auto &c : net->st_clock) c += net->cur.run_step_offset;
+        net->cur.run_step_offset = 0;
         net->run_active = false;
     }
     return SNN_OK;
@@ -1376,7 +1376,7 @@ int graph_rows_io(snn_network *net, uint32_t pre_begin, uint32_t pre_count, floa
     }
     uint32_t bad_host[3] = {0, 0, 0};
     if (set && rc == SNN_OK && copy_sync(net, bad_host, bad, 12, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SNN_ERR_BUFFER_READ, "graph check download failed");
-    if (set) net->counts_dirty = true;
+    if (set) net->cache.counts_dirty = true;
     if (rc == SNN_OK && bad_host[0])
         return fail(SNN_ERR_BAD_ARG, std::to_string(bad_host[0]) + " connected edge(s) carry a NaN weight, e.g. (pre " + std::to_string(bad_host[1]) +
                     ", post " + std::to_string(bad_host[2]) + "): NaN is the absent-edge sentinel of the device matrix, such an edge cannot be "

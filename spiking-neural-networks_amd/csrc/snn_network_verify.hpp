@@ -8,24 +8,8 @@ namespace {
 
 int run_steps(snn_network *net, uint64_t iterations);
 
-// host-side cursors a run moves: what a rollback (or the second pass of "verify") puts back
-struct RunCursors {
-    long long clock, run_step_offset;
-    uint64_t hist_steps, hist_tick, launches, steps, stdp_steps;
-    size_t ev_used;
-};
-RunCursors run_cursors(const snn_network *net)
-{
-    return {net->clock, net->run_step_offset, net->hist_steps, net->hist_tick, net->stat_run_launches, net->stat_run_steps,
-            net->stat_run_stdp_steps, net->ev_used};
-}
-void restore_cursors(snn_network *net, const RunCursors &c)
-{
-    net->clock = c.clock; net->run_step_offset = c.run_step_offset;
-    net->hist_steps = c.hist_steps; net->hist_tick = c.hist_tick;
-    net->stat_run_launches = c.launches; net->stat_run_steps = c.steps; net->stat_run_stdp_steps = c.stdp_steps;
-    net->ev_used = c.ev_used;
-}
+// what a rollback (or the second pass of "verify") puts back on the host: cursors, one-launch run counters, profiling events handed out
+struct RunCursors { Cursors cur; Stats::Run run; size_t ev_used; };
 
 // "verify": the matrices a run with weight updates rewrites (the snapshot table holds the small arrays only): synapse matrix or
 // sparse weights, traces, dw, counters, the weights a one-launch run with STDP leaves behind
@@ -45,7 +29,7 @@ hvec<std::pair<void *, size_t>> verify_matrices(const snn_network *net)
 // only while the matrices fit a side buffer (64 MiB: the networks of the randomized tests)
 bool verify_applies(const snn_network *net)
 {
-    if (!net->verify || net->profile || net->external_stream || net->sharded || !net->nn) return false;
+    if (!net->opt.verify || net->profile || net->external_stream || net->sharded || !net->nn) return false;
     size_t bytes = 0;
     for (const auto &m : verify_matrices(net)) bytes += m.second;
     return bytes <= ((size_t)64 << 20);
@@ -86,17 +70,10 @@ std::string describe_array(const snn_network *net, const void *ptr, uint32_t wor
     return buf;
 }
 
-// what a pass leaves of the caches: are the shadows of the exchange buffer / the cells' two-copy view valid, and which copy is current
-struct CacheFlags {
-    bool shadow_valid, view_dirty;
-    int shadow_cur, view_cur;
-};
-CacheFlags cache_flags(const snn_network *net) { return {net->shadow_valid, net->view_dirty, net->shadow_cur, net->cell_view_cur}; }
-
-// Left out of the comparison of two passes: the chunk partials (scratch of the two-kernel step only), and the shadows / cell views
-// unless both passes left the same copy valid -- a pass that fell back from the one-launch run to one launch per step leaves
+// Left out of the comparison of two passes (a, b: what each left of the caches): the chunk partials (scratch of the two-kernel step
+// only), and the shadows / cell views unless both passes left the same copy valid -- a pass that fell back from the one-launch run to one launch per step leaves
 // them in another state than a pass that did not, and the validity flags say so
-SkipSet verify_skip_set(const snn_network *net, const CacheFlags &a, const CacheFlags &b)
+SkipSet verify_skip_set(const snn_network *net, const CacheState &a, const CacheState &b)
 {
     SkipSet skip{};
     auto leave_out = [&](const void *array) {
@@ -105,7 +82,7 @@ SkipSet verify_skip_set(const snn_network *net, const CacheFlags &a, const Cache
     };
     leave_out(net->part_i); leave_out(net->part_t);
     if (!(a.shadow_valid && b.shadow_valid && a.shadow_cur == b.shadow_cur)) { leave_out(net->shadow[0]); leave_out(net->shadow[1]); }
-    if (!(!a.view_dirty && !b.view_dirty && a.view_cur == b.view_cur)) { leave_out(net->cell_view[0]); leave_out(net->cell_view[1]); }
+    if (!(!a.view_dirty && !b.view_dirty && a.cell_view_cur == b.cell_view_cur)) { leave_out(net->cell_view[0]); leave_out(net->cell_view[1]); }
     return skip;
 }
 
@@ -131,8 +108,8 @@ int run_verified(snn_network *net, uint64_t iterations)
     const uint64_t generation = net->snap_generation;
     const dim3 grid(std::max(1u, std::min(16u, (net->snap_max_words + 1023u) / 1024u)), net->snap_entries);
     uint32_t *start = net->verify_buf, *first = net->verify_buf + net->verify_words;
-    const RunCursors c0 = run_cursors(net);
-    const CacheFlags f0 = cache_flags(net);
+    const RunCursors c0{net->cur, net->stat.run, net->ev_used};
+    const CacheState f0 = net->cache;
     // the matrices (runs with weight updates): [start state | first outcome], one after the other in a side buffer
     const auto matrices = verify_matrices(net);
     size_t big = 0;
@@ -157,8 +134,8 @@ int run_verified(snn_network *net, uint64_t iterations)
         hipLaunchKernelGGL(k_copy_table_alt, grid, dim3(256), 0, net->stream, table, base, outcome, 0);
         hipLaunchKernelGGL(k_copy_table_alt, grid, dim3(256), 0, net->stream, table, base, start, 1);
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        restore_cursors(net, c0);
-        net->shadow_cur = f0.shadow_cur; net->shadow_valid = f0.shadow_valid; net->cell_view_cur = f0.view_cur;
+        net->cur = c0.cur; net->stat.run = c0.run; net->ev_used = c0.ev_used;
+        net->cache.shadow_cur = f0.shadow_cur; net->cache.shadow_valid = f0.shadow_valid; net->cache.cell_view_cur = f0.cell_view_cur;
         net->cells_stepped = false; net->local_inputs_done = false;
         return SNN_OK;
     };
@@ -183,14 +160,14 @@ int run_verified(snn_network *net, uint64_t iterations)
     hipLaunchKernelGGL(k_copy_table_alt, grid, dim3(256), 0, net->stream, table, base, start, 0);
     HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
     TRY(matrices_copy(0, false));
-    const uint64_t gave_up_0 = net->stat_run_fallbacks;
+    const uint64_t gave_up_0 = net->stat.run_fallbacks;
     TRY(run_steps(net, iterations));
     // what the first pass left of the caches and how it stepped: compared only where both passes agree
-    const CacheFlags f1 = cache_flags(net);
-    const uint64_t launches_1 = net->stat_run_launches - c0.launches, gave_up_1 = net->stat_run_fallbacks;
+    const CacheState f1 = net->cache;
+    const uint64_t launches_1 = net->stat.run.launches - c0.run.launches, gave_up_1 = net->stat.run_fallbacks;
     if (net->snap_generation != generation) {
         // the run allocated and laid the table out anew (first one-launch run of a handle): nothing to compare with this time
-        net->stat_verify_skipped += 1;
+        net->stat.verify_skipped += 1;
         return SNN_OK;
     }
     // (a deferred weight update still pending at the end of the first pass belongs to its outcome: applied before the copy)
@@ -202,20 +179,20 @@ int run_verified(snn_network *net, uint64_t iterations)
     TRY(run_steps(net, iterations));
     TRY(flush_rstdp(net));
     TRY(flush_stdp(net));
-    net->stat_verify_runs += 1;
+    net->stat.verify_runs += 1;
     if (net->snap_generation != generation) {
-        net->stat_verify_skipped += 1;
+        net->stat.verify_skipped += 1;
         return SNN_OK;
     }
-    if (net->verify_fault) {          // option "verify_fault" (test hook): the second outcome is not the first
+    if (net->opt.verify_fault) {          // option "verify_fault" (test hook): the second outcome is not the first
         // (values from 2^30: that word of the first matrix -- the weights -- of a handle with weight updates)
-        const bool in_matrix = net->verify_fault >= (1u << 30) && !matrices.empty();
+        const bool in_matrix = net->opt.verify_fault >= (1u << 30) && !matrices.empty();
         hipLaunchKernelGGL(k_flip_bit, dim3(1), dim3(1), 0, net->stream,
                            in_matrix ? static_cast<uint32_t *>(matrices[0].first) : reinterpret_cast<uint32_t *>(net->xbuf),
-                           in_matrix ? (size_t)(net->verify_fault - (1u << 30)) : (size_t)(net->verify_fault - 1));
-        net->verify_fault = 0;
+                           in_matrix ? (size_t)(net->opt.verify_fault - (1u << 30)) : (size_t)(net->opt.verify_fault - 1));
+        net->opt.verify_fault = 0;
     }
-    const CacheFlags f2 = cache_flags(net);
+    const CacheState f2 = net->cache;
     uint32_t report[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     TRY(compare(first, verify_skip_set(net, f1, f2), report));
     if (!report[0]) return SNN_OK;
@@ -225,13 +202,13 @@ int run_verified(snn_network *net, uint64_t iterations)
              (double)__builtin_bit_cast(float, report[3]), report[4], (double)__builtin_bit_cast(float, report[4]));
     const void *arr = (e >= 1 && e <= net->snap_table_host.size()) ? (const void *)net->snap_table_host[e - 1].src
                     : (e >= (1u << 20) && e - (1u << 20) < matrices.size()) ? matrices[e - (1u << 20)].first : nullptr;
-    net->verify_text = "run of " + std::to_string(iterations) + " steps ending at clock " + std::to_string(net->clock) + ": " +
+    net->verify_text = "run of " + std::to_string(iterations) + " steps ending at clock " + std::to_string(net->cur.clock) + ": " +
                        std::to_string(n) + " words differ between two executions from the same state; e.g. " +
                        describe_array(net, arr, w) + ": " + vals;
     net->verify_text += "; first pass: " + std::to_string(launches_1) + " one-launch launches, " + std::to_string(gave_up_1 - gave_up_0) +
-                        " gave up; second pass: " + std::to_string(net->stat_run_launches - c0.launches) + " one-launch launches, " +
-                        std::to_string(net->stat_run_fallbacks - gave_up_1) + " gave up";
-    net->stat_verify_mismatches += 1;
+                        " gave up; second pass: " + std::to_string(net->stat.run.launches - c0.run.launches) + " one-launch launches, " +
+                        std::to_string(net->stat.run_fallbacks - gave_up_1) + " gave up";
+    net->stat.verify_mismatches += 1;
     // Which of the two repeats?  A THIRD execution from the same start (handles without weight updates): the handle keeps its
     // outcome.
     if (matrices.empty()) {
@@ -242,7 +219,7 @@ int run_verified(snn_network *net, uint64_t iterations)
         }
         TRY(rewind(net->verify_third));
         TRY(run_steps(net, iterations));
-        const CacheFlags f3 = cache_flags(net);
+        const CacheState f3 = net->cache;
         uint32_t from_first[8] = {}, from_second[8] = {};
         TRY(compare(first, verify_skip_set(net, f1, f3), from_first));
         TRY(compare(net->verify_third, verify_skip_set(net, f2, f3), from_second));
