@@ -621,7 +621,9 @@ int snn_profile_read_plasticity(snn_network_t *net, uint64_t *steps, double *tot
  * under load.  Applied identically on every shard handle. */
 int snn_set_synthetic_drive(snn_network_t *net, uint64_t seed, float fraction, float voltage);
 /* ALGORITHMIC bytes ONE launch of the synaptic-input kernel moves (DESIGN.md "Roofline"; what the step has to move, not
- * what the counters saw): 4 B per synapse of the shard (dense); 8 B per stored synapse (sparse) + S bytes of state per OWNED
+ * what the counters saw): 4 B per synapse of the shard (dense) -- 3 B while the next plain step reads the 24-bit image of a
+ * static matrix instead of W (built by the first run after the graph was set, so the figure of a handle
+ * that has not run yet is the 4 B one; SNN_AMD_W24=0 keeps W); 8 B per stored synapse (sparse) + S bytes of state per OWNED
  * row when the launch is the one-launch step k_step_csr, which also is the neuron update (S by model: Izhikevich 60, leaky
  * 68, Hodgkin-Huxley 140, ...; + 44 B per live transmitter type with chemical synapses) + 28 B per spike-train cell when
  * the cells advance in that launch too; 16 B per internal synapse of a reward-modulated lattice whose weight update rides

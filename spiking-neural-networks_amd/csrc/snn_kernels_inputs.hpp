@@ -29,7 +29,9 @@
 // ascending sequential f32 accumulation from 0.0f of `term * weight` (no FMA: the TU is built with
 // -ffp-contract=off); absent edges (NaN sentinel) are skipped, not added as zeros.
 #pragma once
+#include <type_traits>
 #include "snn_layout.hpp"
+#include "snn_w24.hpp"
 
 namespace snn {
 
@@ -93,6 +95,7 @@ constexpr int STDP_MAX_LATTICES = 4;
 constexpr uint32_t KIND_NEURON = 0, KIND_ST_SILENT = 1, KIND_ST_FIRED = 2;
 
 typedef float v4f __attribute__((ext_vector_type(4)));
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
 // Two shapes of the same kernel (identical arithmetic, chosen by the size of W):
 //  STREAM  (W larger than the caches): 256 threads, 4 adjacent columns per lane, one
@@ -118,6 +121,12 @@ __device__ __forceinline__ float acc_if_edge(float acc, float term, float w)
     // `w == w` is false exactly for the NaN sentinel of an absent edge
     return (w == w) ? acc + term * w : acc;
 }
+// ... and of the pass over the 24-bit image (snn_w24.hpp): the weight decoded from its code, present unless the code says absent
+struct W24Weight { float w; bool present; };
+__device__ __forceinline__ float acc_if_edge(float acc, float term, W24Weight e)
+{
+    return e.present ? acc + term * e.w : acc;
+}
 
 // NT: number of live transmitter types the launch is specialised on (1..3; only read when CHEM).  A network whose
 // cells all release one type (BASELINE configs[2]: AMPA) then carries VEC accumulators for it instead of 3 * VEC, no
@@ -132,11 +141,19 @@ __device__ __forceinline__ float acc_if_edge(float acc, float term, float w)
 // a column tile goes on to update the tile's neurons)
 // AGENT_STORES: the partials leave as agent-scope relaxed atomic stores (write-through past this XCD's L2), for a reader in the
 // SAME launch on another XCD (k_inputs_dense_close); the plain kernel's partials are read by the next launch and stay ordinary stores
-template <bool ELEC, bool CHEM, int STREAM = 1, int NT = K_TYPES, int STDP = 0, bool AGENT_STORES = false>
-__device__ __forceinline__ void inputs_dense_pass(const InputsArgs &a)
+// W24: the weights come from the 24-bit image of W (`image`, `w24_base`; snn_w24.hpp, k_inputs_dense_w24) -- a row group is a unit of
+// 16 rows in three 16-byte pieces per column instead of 4 rows in one, a weight is its code + base and an absent edge the absent code;
+// staging, row bodies, tile rotation, the early first request and the partial stores are the code of the pass over W
+template <bool ELEC, bool CHEM, int STREAM = 1, int NT = K_TYPES, int STDP = 0, bool AGENT_STORES = false, bool W24 = false>
+__device__ __forceinline__ void inputs_dense_pass(const InputsArgs &a, const v4u *image = nullptr, uint32_t w24_base = 0u)
 {
     using S = InputsShape<STREAM>;
     constexpr int VEC = S::VEC;
+    static_assert(!W24 || (STREAM != 0 && !CHEM && STDP == 0 && !AGENT_STORES), "the image serves the plain streamed electrical pass");
+    using wv = std::conditional_t<W24, v4u, v4f>;            // a 16-byte piece as loaded
+    constexpr int WU = W24 ? 3 * VEC : VEC;                  // pieces of one row group per lane
+    constexpr uint32_t GROUP_ROWS = W24 ? W24_UNIT_ROWS : 4u;
+    constexpr int W24_SERIAL_ROWS = 2;                        // see run_group
     constexpr int TS = CHEM ? NT : 1;                        // transmitter slots of this instantiation
 
     // 16-byte aligned: the 4 rows of a row group are read back with one ds_read_b128 per array
@@ -157,11 +174,12 @@ __device__ __forceinline__ void inputs_dense_pass(const InputsArgs &a)
     // Column tile of this workgroup, rotated by the chunk index: workgroups are dealt round-robin over the 8
     // XCDs, so with a power-of-two tile count an unrotated mapping would pin every XCD (and its L2 / fabric
     // ports) to the same 1/8 of the columns for the whole pass.
-    constexpr uint32_t GB = S::GROUP_BATCH;
+    constexpr uint32_t GB = W24 ? 1u : S::GROUP_BATCH;       // (the image: one unit = 16 rows per register buffer)
     const uint32_t tile = (blockIdx.x + blockIdx.y) % gridDim.x;
     const uint32_t ql = tile * S::TILE + tid;                // the lane's column j is ql + j * THREADS
     const size_t ld = a.ld;
-    const uint32_t groups = (rows + 3u) >> 2;                // row groups of the chunk (rows are padded to 4 with NaN)
+    // row groups of the chunk (rows are padded to 4 with NaN; the image's to 16 with the absent code)
+    const uint32_t groups = W24 ? (rows + W24_UNIT_ROWS - 1u) / W24_UNIT_ROWS : (rows + 3u) >> 2;
     // Addresses = a wave-uniform base (row group, tile, column slot j) + the lane's fixed 16-byte index: no per-lane
     // 64-bit arithmetic in the loop.  A column of the last tile past the shard's width reads into the next row group
     // (or, for the last group, into the slack the matrix is allocated with: WMATRIX_SLACK); the value is never used.
@@ -169,16 +187,32 @@ __device__ __forceinline__ void inputs_dense_pass(const InputsArgs &a)
     bool colv[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) colv[j] = ql + (uint32_t)j * S::THREADS < a.n_loc;
-    auto load_units = [&](uint32_t grp, v4f (&w)[VEC]) {
-        const v4f *gp = ubase + (size_t)grp * ld;
+    // the image, in 16-byte pieces: unit (row unit, column block) at (row unit * ld / 64 + column block) * 192, plane k at + 64 k,
+    // the lane's piece at + lane; the wavefronts of a workgroup take adjacent column blocks, column slot j is 4 blocks further.
+    // Everything but the lane is wave-uniform and stays in scalar registers: a load is scalar base + the lane's 32-bit offset.
+    const uint32_t wave = W24 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)) : 0u, lane = tid & 63u;
+    const v4u *ibase = W24 ? image + ((size_t)(p0 / W24_UNIT_ROWS) * (ld >> 6) + (size_t)tile * (S::TILE / 64) + wave) * 192 : nullptr;
+    auto load_units = [&](uint32_t grp, wv (&w)[WU]) {
+        if constexpr (W24) {
+            const v4u *gp = ibase + (size_t)grp * ld * 3;
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) w[j] = __builtin_nontemporal_load(gp + j * S::THREADS + tid);
+            for (int j = 0; j < VEC; ++j)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) w[j * 3 + k] = __builtin_nontemporal_load(gp + (j * (S::THREADS / 64) * 192 + k * 64) + lane);
+        } else {
+            const v4f *gp = ubase + (size_t)grp * ld;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) w[j] = __builtin_nontemporal_load(gp + j * S::THREADS + tid);
+        }
     };
 
     // The first batch of row groups is requested BEFORE the presynaptic values are staged: all workgroups of a
     // launch start together, and without this the whole chip would leave HBM idle for the staging round trip.
-    v4f pre[GB][VEC];
-    const bool have_pre = groups >= GB && ql < a.n_loc;
+    // (the image: only for chunks whose rows are all neurons -- the per-row-kind sweep of a chunk with spike-train rows then has no
+    // early request to carry through its branches, and the registers of `pre` are the plain loop's first buffer and nothing else)
+    const bool w24_plain = W24 && (p0 + rows <= a.n_neurons);
+    wv pre[GB][WU];
+    const bool have_pre = groups >= GB && ql < a.n_loc && (!W24 || w24_plain);
     if (have_pre) {
 #pragma unroll
         for (uint32_t u = 0; u < GB; ++u) load_units(u, pre[u]);
@@ -228,7 +262,7 @@ __device__ __forceinline__ void inputs_dense_pass(const InputsArgs &a)
         kinds_or |= kind;
     }
     // rows of the chunk's last group past n_tot are padding (their weights are the absent-edge NaN): harmless values
-    for (uint32_t i = rows + tid; i < groups * 4; i += S::THREADS) {
+    for (uint32_t i = rows + tid; i < groups * GROUP_ROWS; i += S::THREADS) {
         s_val[i] = 0.0f;
         s_kind[i] = KIND_NEURON;
         if (STDP == 1) s_rowflag[i] = 0u;
@@ -393,15 +427,47 @@ __device__ __forceinline__ void inputs_dense_pass(const InputsArgs &a)
     // first use, so every wave keeps ROW_BATCH rows of reads per column in flight regardless of the branches in the
     // body.  `body(row, w[VEC])` sees one presynaptic row at a time, as before the quad-row layout.
     auto sweep = [&](auto body) {
-        auto run_group = [&](uint32_t grp, v4f (&wg)[VEC]) {
-            if (STDP == 1 && stdp_live) stdp_group(grp, wg);
-            if (STDP == 2 && rows_live) stdp_rows_group(grp, wg);
+        auto run_group = [&](uint32_t grp, wv (&wg)[WU]) {
+            if constexpr (W24) {
+                // the code of row r of the unit: bytes 3 r .. 3 r + 2 of the lane's 48 -- one byte select over the dword that holds
+                // byte 3 r and its successor (selector 0x0c: a zero byte), then the launch-uniform base
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float w[VEC];
+                for (int r = 0; r < (int)W24_UNIT_ROWS; ++r) {
+                    // Every W24_SERIAL_ROWS rows the sums so far and the dwords the next rows decode pass through an empty asm
+                    // statement: those rows' byte selects cannot start before the previous rows' sums exist.  Left to itself the
+                    // scheduler decodes a whole unit ahead of the sums (64 codes + 64 products live next to the 96 registers of
+                    // the two buffers: 276 registers unbounded, spills under the bound of three wavefronts per SIMD); two rows at
+                    // a time is the granularity that fits 168 registers without a spill (tests/test_isa_w24.py holds it there).
+                    if (r % W24_SERIAL_ROWS == 0) {
 #pragma unroll
-                for (int j = 0; j < VEC; ++j) w[j] = wg[j][k];
-                body(grp * 4 + k, w);
+                        for (int j = 0; j < VEC; ++j) {
+                            const int q0 = (3 * r) >> 2;
+#pragma unroll
+                            for (int q = q0; q < q0 + (3 * W24_SERIAL_ROWS + 3) / 4 && q < 12; ++q)
+                                asm volatile("" : "+v"(acc[j]), "+v"(wg[j * 3 + (q >> 2)][q & 3]));
+                        }
+                    }
+                    const int d0 = (3 * r) >> 2, d1 = d0 < 11 ? d0 + 1 : d0, b = (3 * r) & 3;
+                    const uint32_t sel = 0x0c000000u | (uint32_t)(b + 2) << 16 | (uint32_t)(b + 1) << 8 | (uint32_t)b;
+                    W24Weight w[VEC];
+#pragma unroll
+                    for (int j = 0; j < VEC; ++j) {
+                        const uint32_t code = __builtin_amdgcn_perm(wg[j * 3 + (d1 >> 2)][d1 & 3], wg[j * 3 + (d0 >> 2)][d0 & 3], sel);
+                        w[j].w = __uint_as_float(code + w24_base);
+                        w[j].present = code != W24_ABSENT;
+                    }
+                    body(grp * W24_UNIT_ROWS + r, w);
+                }
+            } else {
+                if (STDP == 1 && stdp_live) stdp_group(grp, wg);
+                if (STDP == 2 && rows_live) stdp_rows_group(grp, wg);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float w[VEC];
+#pragma unroll
+                    for (int j = 0; j < VEC; ++j) w[j] = wg[j][k];
+                    body(grp * 4 + k, w);
+                }
             }
         };
         uint32_t g = 0;
@@ -411,9 +477,9 @@ __device__ __forceinline__ void inputs_dense_pass(const InputsArgs &a)
             // types keep one buffer -- they need the registers for their extra accumulators), -5 % time at 96x96 for
             // the 2-column shape, -24 % at 64x64 for the one-column cache-resident shape (2 x 32 rows).
             constexpr uint32_t B = GB;
-            if (groups >= 2 * B) {
-                v4f (&wa)[B][VEC] = pre;          // groups 0 .. B-1, requested before the staging phase
-                v4f wb[B][VEC];
+            if (groups >= 2 * B && (!W24 || w24_plain)) {
+                wv (&wa)[B][WU] = pre;            // groups 0 .. B-1, requested before the staging phase
+                wv wb[B][WU];
                 for (; g + 3 * B <= groups; g += 2 * B) {
 #pragma unroll
                     for (uint32_t u = 0; u < B; ++u) load_units(g + B + u, wb[u]);
@@ -430,20 +496,27 @@ __device__ __forceinline__ void inputs_dense_pass(const InputsArgs &a)
                 g += B;
             }
         }
-        if (g == 0 && have_pre) {
+        if constexpr (W24) {
+            // (a chunk of one unit: `pre` is consumed here or by the loop above, never both -- said so that the early request's
+            // registers ARE the loop's first buffer instead of living through it for this case)
+            if (w24_plain && groups < 2 * GB) {
+                run_group(0, pre[0]);
+                g = GB;
+            }
+        } else if (g == 0 && have_pre) {
 #pragma unroll
             for (uint32_t u = 0; u < GB; ++u) run_group(u, pre[u]);
             g = GB;
         }
         for (; g + GB <= groups; g += GB) {
-            v4f wb[GB][VEC];
+            wv wb[GB][WU];
 #pragma unroll
             for (uint32_t u = 0; u < GB; ++u) load_units(g + u, wb[u]);
 #pragma unroll
             for (uint32_t u = 0; u < GB; ++u) run_group(g + u, wb[u]);
         }
         for (; g < groups; ++g) {
-            v4f w[VEC];
+            wv w[WU];
             load_units(g, w);
             run_group(g, w);
         }
@@ -452,13 +525,13 @@ __device__ __forceinline__ void inputs_dense_pass(const InputsArgs &a)
     const bool plain = !CHEM && (p0 + rows <= a.n_neurons);   // workgroup-uniform
     if (plain) {
         // all presynaptic rows are neurons, electrical only: the C1/C2 inner loop
-        sweep([&](uint32_t r, const float (&w)[VEC]) {
+        sweep([&](uint32_t r, const auto (&w)[VEC]) {
             const float vp = s_val[r];
 #pragma unroll
             for (int j = 0; j < VEC; ++j) acc[j] = acc_if_edge(acc[j], gq[j] * (vp - vq[j]), w[j]);
         });
     } else if (uniform_chunk) {
-        sweep([&](uint32_t r, const float (&w)[VEC]) {
+        sweep([&](uint32_t r, const auto (&w)[VEC]) {
             if (ELEC) {
                 const float vp = s_val[r];
 #pragma unroll
@@ -474,7 +547,7 @@ __device__ __forceinline__ void inputs_dense_pass(const InputsArgs &a)
             }
         });
     } else {
-        sweep([&](uint32_t r, const float (&w)[VEC]) {
+        sweep([&](uint32_t r, const auto (&w)[VEC]) {
             const uint32_t kind = __builtin_amdgcn_readfirstlane(s_kind[r]);
             if (ELEC) {
                 const float vp = s_val[r];
@@ -529,6 +602,16 @@ template <bool ELEC, bool CHEM, int STREAM = 1, int NT = K_TYPES, int STDP = 0>
 __global__ __launch_bounds__(InputsShape<STREAM>::THREADS, (STDP == 2 && STREAM == 1 && !CHEM) ? 3 : 1) void k_inputs_dense(const InputsArgs a)
 {
     inputs_dense_pass<ELEC, CHEM, STREAM, NT, STDP>(a);
+}
+
+// The plain electrical pass of a handle whose weights are static, over the 24-bit image of W (snn_w24.hpp): 3 bytes per synapse
+// instead of 4, every sum bit for bit the one k_inputs_dense<ELEC, false, STREAM> computes.  Two register buffers of one unit each
+// (12 dwords per column); the launch bound keeps the plain pass's wavefronts per SIMD (three for the 4-column shape, four for the
+// 2-column shape).
+template <bool ELEC, int STREAM>
+__global__ __launch_bounds__(InputsShape<STREAM>::THREADS, STREAM == 1 ? 3 : 4) void k_inputs_dense_w24(const InputsArgs a, const v4u *image, uint32_t base)
+{
+    inputs_dense_pass<ELEC, false, STREAM, K_TYPES, 0, false, true>(a, image, base);
 }
 
 // Static per-column counts, recomputed when the graph or the neurotransmitter flags change:

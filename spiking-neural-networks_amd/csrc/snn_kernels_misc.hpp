@@ -5,6 +5,7 @@
 // column/row updates (neuron/plasticity/mod.rs:45-66 driven as neuron/mod.rs:2308-2417, 2573-2576).
 #pragma once
 #include "snn_layout.hpp"
+#include "snn_w24.hpp"
 #include "snn_math.hpp"
 #include "snn_custom_model.hpp"
 
@@ -140,6 +141,60 @@ __global__ void k_weight_snapshot(const float *W, uint32_t ld, uint32_t first, u
     if (c >= count) return;
     const float w = W[widx(first + r, first + c, ld)];
     dst[(size_t)r * count + c] = (w == w) ? w : 0.0f;
+}
+
+// ---- the 24-bit image of a static matrix (snn_w24.hpp) ---------------------------------------------------------------------
+// smallest and largest bit pattern, compared unsigned, over the present edges of rows [0, n_tot) x columns [0, n_loc):
+// range[0] = min (starts at 0xFFFFFFFF), range[1] = max (starts at 0)
+typedef float w24_v4f __attribute__((ext_vector_type(4)));
+typedef uint32_t w24_v4u __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void k_w24_range(const float *W, uint32_t ld, uint32_t n_loc, uint32_t n_tot, uint32_t *range)
+{
+    const size_t groups = (n_tot + 3u) >> 2, total = groups * n_loc;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t g = i / n_loc, q = i - g * n_loc;
+        const w24_v4f w = reinterpret_cast<const w24_v4f *>(W)[g * ld + q];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t bits = __float_as_uint(w[k]);
+            if (w[k] == w[k] && (uint32_t)(g * 4 + k) < n_tot) { lo = min(lo, bits); hi = max(hi, bits); }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        lo = min(lo, (uint32_t)__shfl_xor((int)lo, off));
+        hi = max(hi, (uint32_t)__shfl_xor((int)hi, off));
+    }
+    if ((threadIdx.x & 63u) == 0u && lo <= hi) { atomicMin(&range[0], lo); atomicMax(&range[1], hi); }
+}
+
+// the image itself: one thread produces one lane's 48 bytes -- 16 rows of one column -- and stores them as three 16-byte pieces
+// (a wavefront's stores are 1 KiB contiguous each); rows past n_tot and columns past n_loc get the absent code.
+// grid (ld / 256 rounded up, row units), 256 threads
+__global__ __launch_bounds__(256) void k_w24_pack(const float *W, uint32_t ld, uint32_t n_loc, uint32_t n_tot, uint32_t base, w24_v4u *image)
+{
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x, ru = blockIdx.y;
+    if (q >= ld) return;
+    const uint32_t groups = (n_tot + 3u) >> 2;
+    uint32_t code[16];
+#pragma unroll
+    for (uint32_t g = 0; g < 4; ++g) {
+        const uint32_t grp = ru * 4u + g;
+        w24_v4f w = {0.0f, 0.0f, 0.0f, 0.0f};
+        const bool in = grp < groups && q < n_loc;
+        if (in) w = reinterpret_cast<const w24_v4f *>(W)[(size_t)grp * ld + q];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            const bool edge = in && grp * 4u + k < n_tot && w[k] == w[k];
+            code[g * 4 + k] = edge ? w24_encode(__float_as_uint(w[k]), base) : W24_ABSENT;
+        }
+    }
+    uint32_t dw[12];
+    w24_pack16(code, dw);
+    w24_v4u *dst = image + ((size_t)ru * (ld >> 6) + (q >> 6)) * 192u + (q & 63u);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dst[k * 64] = w24_v4u{dw[4 * k], dw[4 * k + 1], dw[4 * k + 2], dw[4 * k + 3]};
 }
 
 __global__ void k_graph_synthetic(float *W, uint32_t ld, uint32_t n_loc, uint32_t q0, uint32_t n_neurons,

@@ -45,6 +45,7 @@ int snn_network_create(int device, int neuron_model, int nt_kinetics, int recept
         if (const char *e = r.source != OPTION_ONLY ? getenv(option_env_name(r).c_str()) : nullptr) net->opt.*r.member = option_from_env(r, e);
     net->model = neuron_model; net->nt_kind = nt_kinetics; net->rc_kind = receptor_kinetics;
     net->st_kind = spike_train_model;
+    if (const char *e = getenv("SNN_AMD_W24")) net->w24_enabled = !(e[0] == '0' && e[1] == '\0');      // (outside the option table, like SNN_AMD_CONTIGUOUS)
     if (hipStreamCreateWithFlags(&net->own_stream, hipStreamNonBlocking) != hipSuccess) {
         delete net;
         return fail(SNN_ERR_QUEUE, "hipStreamCreate failed");
@@ -320,6 +321,7 @@ int snn_fill_graph_synthetic(snn_network_t *net, uint64_t seed, float lo, float 
         HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
     }
     net->cache.counts_dirty = true;
+    w24_invalidate(net);
     return SNN_OK;
 }
 ABI_CATCH
@@ -531,6 +533,7 @@ int snn_set_plasticity(snn_network_t *net, uint32_t id, float a_plus, float a_mi
     net->plast_host[l->slot] = (do_plasticity && !(l->slot < net->rm_on_host.size() && (net->rm_on_host[l->slot] & RM_IS_MODULATED))) ? 1u : 0u;
     net->any_plasticity = false;
     for (uint32_t p : net->plast_host) net->any_plasticity |= (p != 0);
+    w24_invalidate(net);                 // weights that may have moved under a rule: the image is packed again if the handle still qualifies
     TRY(end_run(net));
     HIP_TRY(copy_sync(net, net->stdp_dev, net->stdp_host.data(), net->stdp_host.size() * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
     HIP_TRY(copy_sync(net, net->plast_dev, net->plast_host.data(), net->plast_host.size() * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
@@ -555,6 +558,7 @@ int snn_set_bcm(snn_network_t *net, uint32_t id, float decay, float average_scal
     net->plast_host[l->slot] = (do_plasticity && !(l->slot < net->rm_on_host.size() && (net->rm_on_host[l->slot] & RM_IS_MODULATED))) ? 1u : 0u;
     net->any_plasticity = false;
     for (uint32_t p : net->plast_host) net->any_plasticity |= (p != 0);
+    w24_invalidate(net);                 // weights that may have moved under a rule: the image is packed again if the handle still qualifies
     TRY(end_run(net));
     HIP_TRY(copy_sync(net, net->stdp_dev, net->stdp_host.data(), net->stdp_host.size() * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
     HIP_TRY(copy_sync(net, net->plast_dev, net->plast_host.data(), net->plast_host.size() * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
@@ -643,6 +647,7 @@ int snn_set_reward_modulator(snn_network_t *net, uint32_t id, float dopamine, fl
     m[RM_DOPAMINE_BEFORE] = dopamine;
     // bit 0 do_modulation, bit 1 "this is a reward-modulated lattice" (snn_kernels_reward.hpp): the call makes the lattice one for good
     net->rm_on_host[l->slot] = (do_modulation ? RM_DO_MODULATION : 0u) | RM_IS_MODULATED;
+    w24_invalidate(net);
     net->any_modulation = net->any_modulated = false;
     for (uint32_t v : net->rm_on_host) { net->any_modulation |= (v & RM_DO_MODULATION) != 0; net->any_modulated |= (v & RM_IS_MODULATED) != 0; }
     {
@@ -1163,6 +1168,7 @@ int snn_debug_checkpoint(snn_network_t *net, int restore) ABI_TRY
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
     TRY(end_run(net));
     if (restore) net->img_stale = net->img_stale_direct = true;          // the sparse weights come back: the step image's records are rebuilt
+    if (restore) w24_invalidate(net);                                    // ... and so is the 24-bit image of the dense ones
     auto &cp = net->checkpoint;
     hvec<std::pair<void *, size_t>> arrays;
     for (const auto &r : net->registry)
@@ -2068,6 +2074,7 @@ int snn_input_kernel_bytes(const snn_network_t *net, uint64_t *bytes) ABI_TRY
         return SNN_OK;
     }
     uint64_t b = (uint64_t)4 * net->n_tot * net->n_loc;                    // dense: every weight of the shard, read once
+    if (net->w24_valid && w24_applies(net)) b = (uint64_t)3 * net->n_tot * net->n_loc;      // ... from its 24-bit image (snn_w24.hpp)
     if (net->any_modulation && net->opt.defer_rstdp) {
         // k_inputs_rstdp: the internal edges of a reward-modulated lattice are read AND rewritten, weight and trace --
         // 16 B per synapse instead of 4

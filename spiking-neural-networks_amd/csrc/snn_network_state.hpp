@@ -359,6 +359,14 @@ struct snn_network {
     uint64_t sell_entries = 0;
     hvec<uint32_t> edge_slot_host;   // CSR edge -> SELL entry (for snn_get_graph_csr)
     float *W = nullptr;
+    // The 24-bit image of W (snn_w24.hpp; ensure_w24, snn_network_step.hpp): what the plain electrical pass of a handle with static
+    // weights streams instead of W.  Scratch, not state: owned here and outside the registry, so neither a snapshot nor a checkpoint
+    // copies it -- whatever may change W marks it stale (w24_invalidate) and the next run packs it again.
+    dev_ptr<uint32_t> w24, w24_range;      // the image; the two words of k_w24_range
+    uint32_t w24_base = 0;
+    bool w24_valid = false;                // the image holds W as it is now
+    bool w24_refused = false;              // W as it is now cannot be encoded, or the image could not be allocated: not tried again until W changes
+    bool w24_enabled = true;               // SNN_AMD_W24=0 (A/B runs) keeps the pass on W; read when the handle is created
     float *xbuf = nullptr;
     float *part_i = nullptr, *part_t = nullptr;
     uint32_t *n_in = nullptr, *tcount = nullptr;
@@ -532,6 +540,9 @@ inline bool record_now(const snn_network *net)
 } // namespace
 
 namespace {
+
+// something may have changed a weight: the 24-bit image of W is behind (and a refusal is reconsidered)
+inline void w24_invalidate(snn_network *net) { net->w24_valid = false; net->w24_refused = false; }
 
 // Big streamed arrays (the synapse matrix, the trace matrix).  SNN_AMD_CONTIGUOUS=1 asks for PHYSICALLY CONTIGUOUS memory
 // first (larger page-table fragments).  Off by default: it is not a uniform gain -- C3's input pass 164.4 against 171.3 us in
@@ -1123,6 +1134,7 @@ int build_state(snn_network *net)
     TRY(dev_alloc_t(net, &net->n_in, net->ld));
     TRY(dev_alloc_t(net, &net->tcount, (size_t)K_TYPES * net->ld));
     net->cache.counts_dirty = true;
+    w24_invalidate(net);
     HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
     return SNN_OK;
 }

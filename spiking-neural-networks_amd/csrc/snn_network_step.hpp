@@ -121,8 +121,18 @@ void local_chunks(const snn_network *net, uint32_t *begin, uint32_t *count)
     *count = ce > cb ? ce - cb : 0;
 }
 
-// the dense input pass in one of its three forms: applying the STDP update the previous step deferred, applying its
-// reward-modulated update, or plain
+// The 24-bit image of W (snn_w24.hpp) serves the plain electrical pass of an unsharded dense handle whose matrix is streamed and
+// whose weights nothing rewrites: no plasticity, no reward modulation (of lattices or connections), no weight history; handles
+// the closing pass serves keep W.  SNN_AMD_W24=0 switches it off.
+bool dense_close_applies(const snn_network *net);
+bool w24_applies(const snn_network *net)
+{
+    return net->w24_enabled && !net->csr && !net->sharded && net->n_loc && net->n_tot && matrix_streamed(net) && net->electrical && !net->chemical &&
+           !net->any_plasticity && !net->any_modulation && !net->any_conn_kind && !net->any_whist && !dense_close_applies(net);
+}
+
+// the dense input pass in one of its forms: applying the STDP update the previous step deferred, applying its
+// reward-modulated update, plain over the 24-bit image, or plain over W
 int launch_inputs_dense(snn_network *net, InputsPart part, InputsArgs &a, uint32_t grid_chunks)
 {
     // shape of the pass: cache-resident matrices take the latency-oriented one-wave shape; streamed matrices the
@@ -173,6 +183,15 @@ int launch_inputs_dense(snn_network *net, InputsPart part, InputsArgs &a, uint32
                 in_shape(SH, [&](dim3 grid, dim3 block) {
                     hipLaunchKernelGGL((k_inputs_rstdp<E(), C(), SH()>), grid, block, 0, net->stream, ra);
                 });
+            });
+        });
+    } else if (net->w24_valid && net->w24 && part == INPUTS_ALL && shape != 0 && net->electrical && !net->chemical) {
+        // static weights: 3 bytes per synapse from the image instead of 4 from W, the same sums
+        const v4u *image = reinterpret_cast<const v4u *>(net->w24.get());
+        const uint32_t base = net->w24_base;
+        for_value<1, 2>(shape, [&](auto SH) {
+            in_shape(SH, [&](dim3 grid, dim3 block) {
+                hipLaunchKernelGGL((k_inputs_dense_w24<true, SH()>), grid, block, 0, net->stream, a, image, base);
             });
         });
     } else {
@@ -570,6 +589,7 @@ int choose_matrix_placement(snn_network *net)
                 fprintf(stderr, "[snn] matrix placement: held %p %.3f ms, candidate %p %.3f ms\n", (void *)a, best_ms, b.get(), ms_b);
             if (rc == SNN_OK && ms_b < best_ms * 0.99f) {       // the candidate wins: the registry holds it in place of the old one
                 losers.push_back(dev_replace(net, a, std::move(b)));
+                w24_invalidate(net);
                 best_ms = ms_b;
             } else {
                 net->W = a;
@@ -584,6 +604,65 @@ int choose_matrix_placement(snn_network *net)
                            reinterpret_cast<uint32_t *>(net->W), count, 0x7FC00000u);
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
         HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
+    }
+    return SNN_OK;
+}
+
+// Builds the 24-bit image of W when the next steps would read it (w24_applies) and it is missing or stale: one pass over W for the
+// range of the present weights' bit patterns, one that packs -- a few ms, once per graph.  A matrix that cannot be encoded (mixed
+// signs, a range of 2^24 patterns or more) or an image that cannot be allocated leaves the handle on W, silently.  A handle that
+// stopped qualifying frees the image.
+// Like W's (choose_matrix_placement), the image's HBM placement decides a few per cent of the pass: images of 1 GiB and more are
+// tried in up to two further allocations, filled by device-to-device copy and timed with the real kernel; the fastest stays
+// (1 % rule), the losers are freed after the search, and the search stops when free memory is short.
+int ensure_w24(snn_network *net)
+{
+    if (!w24_applies(net)) {
+        net->w24 = nullptr;
+        w24_invalidate(net);
+        return SNN_OK;
+    }
+    if (net->w24_valid || net->w24_refused) return SNN_OK;
+    auto refuse = [&]() { (void)hipGetLastError(); net->w24 = nullptr; net->w24_refused = true; return SNN_OK; };
+    if (!net->w24_range && snn_malloc(&net->w24_range, 256) != hipSuccess) return refuse();
+    uint32_t range[2] = {0xFFFFFFFFu, 0u};
+    HIP_TRY(copy_sync(net, net->w24_range, range, 8, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+    hipLaunchKernelGGL(k_w24_range, dim3(4096), dim3(256), 0, net->stream, net->W, net->ld, net->n_loc, net->n_tot, net->w24_range.get());
+    HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+    HIP_TRY(copy_sync(net, range, net->w24_range, 8, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    if (!w24_encodable(range[0], range[1])) return refuse();
+    const size_t bytes = w24_image_bytes(net->n_tot, net->ld);
+    if (!net->w24 && alloc_streamed(&net->w24, bytes) != hipSuccess) return refuse();
+    net->w24_base = w24_base(range[0], range[1]);
+    hipLaunchKernelGGL(k_w24_pack, dim3((net->ld + 255) / 256, (unsigned)w24_row_units(net->n_tot)), dim3(256), 0, net->stream,
+                       net->W, net->ld, net->n_loc, net->n_tot, net->w24_base, reinterpret_cast<w24_v4u *>(net->w24.get()));
+    HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+    net->w24_valid = true;
+    if (bytes >= ((size_t)1 << 30)) {
+        const int prof = net->profile;
+        net->profile = 0;
+        float best_ms = 0.0f;
+        int rc = time_input_pass(net, &best_ms);
+        hvec<dev_ptr<uint32_t>> losers;
+        for (int cand = 0; cand < 2 && rc == SNN_OK; ++cand) {
+            size_t free_b = 0, total_b = 0;
+            dev_ptr<uint32_t> b;
+            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + (bytes >> 2) || alloc_streamed(&b, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                break;
+            }
+            if (hipMemcpyAsync(b, net->w24, bytes, hipMemcpyDeviceToDevice, net->stream) != hipSuccess) { losers.push_back(std::move(b)); break; }
+            std::swap(net->w24, b);                              // (b: the image held so far)
+            float ms_b = 0.0f;
+            rc = time_input_pass(net, &ms_b);
+            if (getenv("SNN_DEBUG_PLACEMENT"))
+                fprintf(stderr, "[snn] image placement: held %p %.3f ms, candidate %p %.3f ms\n", (void *)b.get(), best_ms, (void *)net->w24.get(), ms_b);
+            if (rc == SNN_OK && ms_b < best_ms * 0.99f) best_ms = ms_b;
+            else std::swap(net->w24, b);
+            losers.push_back(std::move(b));
+        }
+        net->profile = prof;
+        if (rc != SNN_OK) return rc;
     }
     return SNN_OK;
 }
@@ -931,6 +1010,7 @@ int launch_run_resident(snn_network *net, uint64_t iterations, uint64_t steps_be
             if (net->run_failed[0]) return SNN_OK;
             HIP_TRY(hipMemcpyAsync(net->W, net->run_w_out, (size_t)4 * ((net->n_tot + 3) / 4) * net->ld * 4, hipMemcpyDeviceToDevice, net->stream),
                     SNN_ERR_BUFFER_WRITE);
+            w24_invalidate(net);
             net->cur.clock += steps - 1;
             TRY(launch_plasticity(net));
             net->cur.clock -= steps - 1;
@@ -1259,6 +1339,7 @@ int grow_history(snn_network *net, uint64_t extra)
 int begin_run(snn_network *net, uint64_t iterations)
 {
     TRY(ensure_counts(net));
+    TRY(ensure_w24(net));
     TRY(ensure_uniform_tables(net));
     TRY(ensure_exchange_plan(net));
     if ((net->want_avg || net->want_eeg) && net->sharded && net->n_shards > 1 &&
@@ -1376,7 +1457,7 @@ int graph_rows_io(snn_network *net, uint32_t pre_begin, uint32_t pre_count, floa
     }
     uint32_t bad_host[3] = {0, 0, 0};
     if (set && rc == SNN_OK && copy_sync(net, bad_host, bad, 12, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SNN_ERR_BUFFER_READ, "graph check download failed");
-    if (set) net->cache.counts_dirty = true;
+    if (set) { net->cache.counts_dirty = true; w24_invalidate(net); }
     if (rc == SNN_OK && bad_host[0])
         return fail(SNN_ERR_BAD_ARG, std::to_string(bad_host[0]) + " connected edge(s) carry a NaN weight, e.g. (pre " + std::to_string(bad_host[1]) +
                     ", post " + std::to_string(bad_host[2]) + "): NaN is the absent-edge sentinel of the device matrix, such an edge cannot be "

@@ -47,7 +47,7 @@ std::string describe_array(const snn_network *net, const void *ptr, uint32_t wor
     for (int i = 0; i < 2; ++i)
         if (inside(net->cell_view[i], (size_t)net->c_pad * 8)) return "cell view " + std::to_string(i) + ", word " + std::to_string(word);
     const struct { const void *base; const char *name; } known[] = {
-        {net->part_i, "part_i"}, {net->part_t, "part_t"}, {net->n_in, "n_in"}, {net->tcount, "tcount"}, {net->W, "W"},
+        {net->part_i, "part_i"}, {net->part_t, "part_t"}, {net->n_in, "n_in"}, {net->tcount, "tcount"}, {net->W, "W"}, {net->w24, "24-bit image of W"},
         {net->spike_counts, "spike_counts"}, {net->spike_count, "spike_count"}, {net->st_clock_dev, "st_clock_dev"},
         {net->uni_neuron, "uniform table (neurons)"}, {net->uni_cell, "uniform table (cells)"}, {net->ca.presyn_value, "cells: presyn_value"},
         {net->ca.seed, "cells: seed"}, {net->ca.step, "cells: step"}, {net->ca.counter, "cells: counter"}, {net->lattice_slot, "lattice_slot"},
@@ -121,7 +121,7 @@ int run_verified(snn_network *net, uint64_t iterations)
     }
     auto matrices_copy = [&](int half, bool restore) -> int {
         size_t off = (size_t)half * net->verify_big_bytes;
-        if (restore) net->img_stale = net->img_stale_direct = true;
+        if (restore) { net->img_stale = net->img_stale_direct = true; w24_invalidate(net); }
         for (const auto &m : matrices) {
             void *side = net->verify_big + off;
             HIP_TRY(hipMemcpyAsync(restore ? m.first : side, restore ? side : m.first, m.second, hipMemcpyDeviceToDevice, net->stream), SNN_ERR_BUFFER_WRITE);
@@ -190,6 +190,7 @@ int run_verified(snn_network *net, uint64_t iterations)
         hipLaunchKernelGGL(k_flip_bit, dim3(1), dim3(1), 0, net->stream,
                            in_matrix ? static_cast<uint32_t *>(matrices[0].first) : reinterpret_cast<uint32_t *>(net->xbuf),
                            in_matrix ? (size_t)(net->opt.verify_fault - (1u << 30)) : (size_t)(net->opt.verify_fault - 1));
+        if (in_matrix) w24_invalidate(net);
         net->opt.verify_fault = 0;
     }
     const CacheState f2 = net->cache;
