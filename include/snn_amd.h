@@ -171,6 +171,36 @@ int snn_get_graph_rows(snn_network_t *net, uint32_t pre_begin, uint32_t pre_coun
  * connected unless pre == post (or always, with_diagonal != 0).  Nothing crosses PCIe. */
 int snn_fill_graph_synthetic(snn_network_t *net, uint64_t seed, float lo, float hi, int with_diagonal);
 
+/* Connect by rule, evaluated on the device (dense handles): the reference's connect(&|x, y| ..., Some(&|x, y| ...)) inside a
+ * lattice or between two of them (Lattice::connect neuron/mod.rs:1134-1157, LatticeNetwork::connect neuron/mod.rs:1845-1935; the
+ * Python classes' interface_gpu/lixirnet/src/lattices/mod.rs:314-568) for the predicates its users write.  EVERY pair (pre
+ * position a of lattice pre_id, post position b of lattice post_id) is handled once: Some(weight) where the rule holds, None
+ * where it does not; nothing outside that block of the matrix changes and nothing of size N^2 exists on the host.
+ * pre_id == post_id connects a lattice internally; pre_id may be a spike-train lattice, post_id may not.
+ * A position is (row, col) = (i / cols, i % cols) of the lattice-local index i; the pair index is
+ * idx = (uint64_t)i_pre * count_post + i_post, whatever the lattices' places in the network or the shard.
+ * With dr = |a.row - b.row|, dc = |a.col - b.col| the geometric part is
+ *   SNN_RULE_ALL            true
+ *   SNN_RULE_CHEBYSHEV      max(dr, dc) <= extent
+ *   SNN_RULE_EUCLIDEAN      dr*dr + dc*dc <= extent   (the SQUARED radius; integer arithmetic)
+ *   SNN_RULE_SAME_POSITION  a == b
+ * AND, with self_edges == 0, a != b (the reference's x != y: positions, also between two lattices)
+ * AND, when 0 < probability < 1, (float)(hash(edge_seed, idx) >> 8) * 2^-24 < probability -- the splitmix64 generator of
+ * snn_fill_graph_synthetic; probability >= 1 draws nothing, probability <= 0 gives no edge, NaN is SNN_ERR_BAD_ARG.
+ * The weight: SNN_WEIGHT_CONSTANT w_lo; SNN_WEIGHT_UNIFORM w_lo + (w_hi - w_lo) * u24(hash(weight_seed, idx)) as
+ * snn_fill_graph_synthetic computes it (on a single-lattice handle without cells, SNN_RULE_ALL without self edges and
+ * SNN_WEIGHT_UNIFORM write the bits of snn_fill_graph_synthetic(weight_seed, w_lo, w_hi, 0)).
+ * A shard handle writes the columns it owns.  Traces, dw and counters of the block's edges (reward-modulated handles) restart
+ * at 0.  Refused, with the graph as it was and the argument named by snn_last_error: a handle that is not finalized or holds a
+ * sparse graph (SNN_ERR_BAD_STATE: dense handles only); an unknown id, a postsynaptic spike-train lattice, an unknown rule or
+ * weight_rule, a non-finite w_lo / w_hi or, with SNN_WEIGHT_UNIFORM, a w_hi - w_lo that overflows -- NaN is the absent-edge
+ * sentinel -- (SNN_ERR_BAD_ARG). */
+typedef enum { SNN_RULE_ALL = 0, SNN_RULE_CHEBYSHEV = 1, SNN_RULE_EUCLIDEAN = 2, SNN_RULE_SAME_POSITION = 3 } snn_connection_rule;
+typedef enum { SNN_WEIGHT_CONSTANT = 0, SNN_WEIGHT_UNIFORM = 1 } snn_weight_rule;
+int snn_connect_by_rule(snn_network_t *net, uint32_t pre_id, uint32_t post_id, uint32_t rule, uint32_t extent,
+                        int self_edges, float probability, uint64_t edge_seed, uint32_t weight_rule, float w_lo,
+                        float w_hi, uint64_t weight_seed);
+
 /* Sparse form, CSR by LOCAL postsynaptic neuron (the reference's sparse graph, AdjacencyList
  * graph/mod.rs:974-1118, has no GPU form; needed where a dense N x N matrix cannot exist, e.g.
  * BASELINE configs[4]).  snn_network_use_csr must precede finalize; a handle is dense or CSR for life.

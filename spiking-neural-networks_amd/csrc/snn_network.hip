@@ -326,6 +326,59 @@ int snn_fill_graph_synthetic(snn_network_t *net, uint64_t seed, float lo, float 
 }
 ABI_CATCH
 
+int snn_connect_by_rule(snn_network_t *net, uint32_t pre_id, uint32_t post_id, uint32_t rule, uint32_t extent,
+                        int self_edges, float probability, uint64_t edge_seed, uint32_t weight_rule, float w_lo,
+                        float w_hi, uint64_t weight_seed) ABI_TRY
+{
+    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
+    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
+    if (net->csr) return fail(SNN_ERR_BAD_STATE, "connecting by rule is for dense handles only: this handle holds a sparse graph");
+    const LatticeInfo *pre = find_lattice(net, pre_id), *post = find_lattice(net, post_id);
+    if (!pre) return fail(SNN_ERR_BAD_ARG, "pre_id: unknown lattice id " + std::to_string(pre_id));
+    if (!post) return fail(SNN_ERR_BAD_ARG, "post_id: unknown lattice id " + std::to_string(post_id));
+    if (post->spike_train)   // LatticeNetworkError::PostsynapticLatticeCannotBeSpikeTrain, neuron/mod.rs:1852-1854
+        return fail(SNN_ERR_BAD_ARG, "post_id: lattice " + std::to_string(post_id) + " is a spike-train lattice, which is never postsynaptic");
+    if (rule >= CONNECT_RULES) return fail(SNN_ERR_BAD_ARG, "rule: unknown connection rule " + std::to_string(rule));
+    if (weight_rule >= CONNECT_WEIGHTS) return fail(SNN_ERR_BAD_ARG, "weight_rule: unknown weight rule " + std::to_string(weight_rule));
+    if (probability != probability) return fail(SNN_ERR_BAD_ARG, "probability is NaN");
+    if (w_lo - w_lo != 0.0f) return fail(SNN_ERR_BAD_ARG, "w_lo is not finite (NaN is the absent-edge sentinel of the device matrix)");
+    if (w_hi - w_hi != 0.0f) return fail(SNN_ERR_BAD_ARG, "w_hi is not finite (NaN is the absent-edge sentinel of the device matrix)");
+    if (weight_rule == CONNECT_UNIFORM && (w_hi - w_lo) - (w_hi - w_lo) != 0.0f)      // (lo + inf * u24 is +-inf, or NaN where u24 is 0)
+        return fail(SNN_ERR_BAD_ARG, "w_hi - w_lo is not finite: the uniform weights would be infinite or the absent-edge sentinel");
+    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
+    TRY(end_run(net));                     // a deferred reward-modulated update belongs to the OLD weights: apply it first
+    net->cross_checked = false;
+    net->cache.counts_dirty = true;        // stale from here on, whichever way the call ends (as graph_rows_io marks them on every exit of a set)
+    w24_invalidate(net);
+    // the block's columns this handle owns, as local columns
+    const uint32_t c_begin = std::max(post->first, net->q0), c_end = std::min(post->first + post->count, net->q0 + net->n_loc);
+    if (pre->count && c_begin < c_end) {
+        ConnectArgs a{};
+        a.W = net->W; a.ld = net->ld;
+        a.col0 = c_begin - net->q0; a.n_cols = c_end - c_begin; a.post_i0 = c_begin - post->first;
+        a.post_cols = post->cols; a.post_count = post->count;
+        a.pre_first = pre->first; a.pre_count = pre->count; a.pre_rows = pre->rows; a.pre_cols = pre->cols;
+        a.extent = extent; a.probability = probability; a.edge_seed = edge_seed; a.weight_seed = weight_seed;
+        a.w_lo = w_lo; a.w_hi = w_hi;
+        const uint32_t groups = ((a.pre_first + a.pre_count - 1u) >> 2) - (a.pre_first >> 2) + 1u;
+        const uint32_t blocks_x = (a.col0 + a.n_cols - (a.col0 & ~63u) + 255u) / 256u;
+        // (probability <= 0: the draw is made and never succeeds)
+        hipLaunchKernelGGL(connect_kernel((int)rule, (int)weight_rule, probability < 1.0f, self_edges != 0),
+                           dim3(blocks_x, std::min<uint32_t>(groups, 4096)), dim3(256), 0, net->stream, a);
+        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+        // a replaced edge starts with a fresh TraceRSTDP; the other blocks keep theirs
+        for (float *m : {net->trace.get(), net->pending.get(), net->edge_counter.get()})
+            if (m) {
+                hipLaunchKernelGGL(k_connect_clear, dim3(blocks_x, std::min<uint32_t>(groups, 4096)), dim3(256), 0,
+                                   net->stream, m, net->ld, a.col0, a.n_cols, a.pre_first, a.pre_count);
+                HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+            }
+        HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
+    }
+    return SNN_OK;
+}
+ABI_CATCH
+
 int snn_network_use_csr(snn_network_t *net, int enable) ABI_TRY
 {
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");

@@ -606,6 +606,17 @@ public:
     }
     snn_network_t *handle() const { return h_; }
 
+    // connect(...) of the reference (neuron/mod.rs:1134-1157, 1845-1935) for the predicates snn_connect_by_rule evaluates on the
+    // device: lattice `pre` into neuron lattice `post` (the same id: internally).  The graph changes on the device only; sync()
+    // brings it into `network`.
+    void connect_by_rule(size_t pre, size_t post, uint32_t rule, uint32_t extent = 0, bool self_edges = true, float probability = 1.0f,
+                         uint64_t edge_seed = 0, uint32_t weight_rule = SNN_WEIGHT_CONSTANT, float w_lo = 1.0f, float w_hi = 1.0f,
+                         uint64_t weight_seed = 0)
+    {
+        check(snn_connect_by_rule(h_, (uint32_t)pre, (uint32_t)post, rule, extent, self_edges, probability, edge_seed, weight_rule,
+                                  w_lo, w_hi, weight_seed));
+    }
+
   private:
     template <class V>
     std::vector<std::vector<V>> cross_rows(size_t pre, size_t post, bool counter)

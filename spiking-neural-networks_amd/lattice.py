@@ -18,7 +18,20 @@ from .network import (CUSTOM, NT_CUSTOM, RC_CUSTOM, REFRACTORINESS_CUSTOM, ST_CU
                       DeviceNetwork, HODGKIN_HUXLEY, IZHIKEVICH, LIF, QUADRATIC_INTEGRATE_AND_FIRE, SIMPLE_LIF,
                       ADAPTIVE_LIF, ADAPTIVE_EXP_LIF, LEAKY_IZHIKEVICH,
                       NT_APPROXIMATE, NT_DESTEXHE,
-                      RC_APPROXIMATE, RC_DESTEXHE, ST_NONE, ST_POISSON, ST_RATE)
+                      RC_APPROXIMATE, RC_DESTEXHE, ST_NONE, ST_POISSON, ST_RATE, ConnectionRule, WeightRule)
+
+
+def _rule_graph(rule, weight, pre_shape, post_shape):
+    """(mask, weights) of a ConnectionRule / WeightRule pair on two grids: what snn_connect_by_rule writes on the device,
+    from the records' host twins.  None when the arguments are the reference's two closures."""
+    if not isinstance(rule, ConnectionRule):
+        if isinstance(weight, WeightRule):
+            raise TypeError("a WeightRule goes with a ConnectionRule, not with a closure")
+        return None
+    if weight is not None and not isinstance(weight, WeightRule):
+        raise TypeError("a ConnectionRule goes with a WeightRule (or None: every edge weighs 1), not with a closure")
+    weight = WeightRule.constant(1.0) if weight is None else weight
+    return rule.mask(pre_shape, post_shape), weight.values(pre_shape, post_shape)
 
 
 class IonotropicNeurotransmitterType(enum.IntEnum):      # iterate_and_spike/mod.rs:1068-1073
@@ -474,6 +487,14 @@ class Lattice:
         self.connections = np.zeros((n, n), np.uint32)
 
     def connect(self, connection_conditional, weight_logic=None):   # neuron/mod.rs:1134-1157
+        """two closures on positions as in the reference, or a ConnectionRule and a WeightRule (the graph the device call
+        DeviceNetwork.connect_by_rule produces, without a Python call per pair)"""
+        graph = _rule_graph(connection_conditional, weight_logic, (self.rows, self.cols), (self.rows, self.cols))
+        if graph is not None:
+            on, w = graph
+            self.connections[...] = on
+            self.weights[...] = np.where(on, w, np.float32(0))
+            return
         pos = [(r, c) for r in range(self.rows) for c in range(self.cols)]
         for i, a in enumerate(pos):
             for j, b in enumerate(pos):
@@ -555,6 +576,13 @@ class RewardModulatedLattice(Lattice):
         self.traces = np.zeros_like(self.weights)
 
     def connect(self, connection_conditional, weight_logic=None):      # neuron/mod.rs:3301-3321
+        graph = _rule_graph(connection_conditional, weight_logic, (self.rows, self.cols), (self.rows, self.cols))
+        if graph is not None:                                              # every edge a fresh TraceRSTDP of that weight
+            on, w = graph
+            self.connections[...] = on
+            self.weights[...] = np.where(on, w, np.float32(0))
+            self.traces[...] = 0
+            return
         pos = [(r, c) for r in range(self.rows) for c in range(self.cols)]
         for i, a in enumerate(pos):
             for j, b in enumerate(pos):
@@ -674,6 +702,9 @@ class LatticeNetwork:
             return self.connect_internally(presynaptic_id, connection_conditional, weight_logic)
         pre = self.lattices.get(presynaptic_id) or self.spike_train_lattices[presynaptic_id]
         post = self.lattices[postsynaptic_id]
+        graph = _rule_graph(connection_conditional, weight_logic, (pre.rows, pre.cols), (post.rows, post.cols))
+        if graph is not None:
+            return self._connect_graph(presynaptic_id, pre, postsynaptic_id, post, *graph)
         for a in ((r, c) for r in range(pre.rows) for c in range(pre.cols)):
             for b in ((r, c) for r in range(post.rows) for c in range(post.cols)):
                 key = (GraphPosition(presynaptic_id, a), GraphPosition(postsynaptic_id, b))
@@ -685,6 +716,25 @@ class LatticeNetwork:
                     self.connecting[key] = 1.0 if weight_logic is None else float(weight_logic(a, b))
                 else:
                     self.connecting.pop(key, None)
+
+    def _connect_graph(self, presynaptic_id, pre, postsynaptic_id, post, on, w):
+        """the closure form's effect for a mask / weight matrix [n_pre, n_post]: the same nodes in the same order, the same edges"""
+        pre_nodes = [GraphPosition(presynaptic_id, (r, c)) for r in range(pre.rows) for c in range(pre.cols)]
+        post_nodes = [GraphPosition(postsynaptic_id, (r, c)) for r in range(post.rows) for c in range(post.cols)]
+        if pre_nodes and post_nodes:
+            # add_node in the order the pair loop meets them: the first pre, every post, then the other pres
+            for node in [pre_nodes[0]] + post_nodes + pre_nodes[1:]:
+                if node not in self._node_set():
+                    self.connecting_nodes.append(node)
+                    self._nodes.add(node)
+        had = bool(self.connecting)
+        for i, a in enumerate(pre_nodes):
+            row_on, row_w = on[i], w[i]
+            for j in np.nonzero(row_on)[0]:
+                self.connecting[(a, post_nodes[j])] = float(row_w[j])
+            if had:
+                for j in np.nonzero(~row_on)[0]:
+                    self.connecting.pop((a, post_nodes[j]), None)
 
     def set_dt(self, dt):
         for l in list(self.lattices.values()) + list(self.spike_train_lattices.values()):

@@ -28,6 +28,8 @@ _NAMES = ("IzhikevichNeuron", "BoundedNeurotransmitterKinetics", "BoundedRecepto
           "STDP", "IzhikevichNeuronLattice", "IzhikevichNeuronLatticeGPU", "DeltaDiracRefractoriness", "RateSpikeTrain",
           "RateSpikeTrainLattice", "GraphPosition", "IzhikevichNeuronNetwork", "IzhikevichNeuronNetworkGPU")
 __all__ = list(_NAMES)
+# not among the reference's names: the records its connect(...) methods take here in place of the two closures
+ConnectionRule, WeightRule = _l.ConnectionRule, _l.WeightRule
 _built = None
 
 

@@ -42,6 +42,119 @@ def _out(shape, dtype=np.float32):
     return a
 _PTR = {"f32": _lib.f32p, "u32": _lib.u32p, "i32": _lib.i32p}
 
+RULE_ALL, RULE_CHEBYSHEV, RULE_EUCLIDEAN, RULE_SAME_POSITION = 0, 1, 2, 3      # snn_connection_rule
+WEIGHT_CONSTANT, WEIGHT_UNIFORM = 0, 1                                         # snn_weight_rule
+
+
+def _pair_grid(pre_shape, post_shape):
+    """positions and pair index of every (pre, post) pair of two grids (rows, cols): pre row / col as columns [n_pre, 1], post
+    row / col as rows [1, n_post], idx = i_pre * n_post + i_post as uint64 [n_pre, n_post]"""
+    (pr, pc), (qr, qc) = pre_shape, post_shape
+    i, j = np.arange(pr * pc, dtype=np.int64)[:, None], np.arange(qr * qc, dtype=np.int64)[None, :]
+    idx = i.astype(np.uint64) * np.uint64(qr * qc) + j.astype(np.uint64)
+    return i // max(pc, 1), i % max(pc, 1), j // max(qc, 1), j % max(qc, 1), idx
+
+
+def _u24(seed, idx):
+    """(float)(hash32(seed, idx) >> 8) * 2^-24 in float32, as csrc/snn_math.hpp computes it"""
+    from . import synthetic
+    return (synthetic.hash32(seed, idx) >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+
+
+class ConnectionRule:
+    """Which pairs (pre position, post position) of two lattices are connected: the predicates the reference's users hand to
+    connect(&|x, y| ...) (neuron/mod.rs:1134-1157, 1845-1935), as data the device evaluates (snn_connect_by_rule of
+    include/snn_amd.h, whose wording `mask` restates in numpy).  kind RULE_ALL | RULE_CHEBYSHEV (max(dr, dc) <= extent) |
+    RULE_EUCLIDEAN (dr^2 + dc^2 <= extent, the squared radius) | RULE_SAME_POSITION; self_edges=False is `x != y`;
+    0 < probability < 1 adds a coin flip per pair drawn from `seed`."""
+
+    def __init__(self, kind, extent=0, self_edges=True, probability=1.0, seed=0):
+        if kind not in (RULE_ALL, RULE_CHEBYSHEV, RULE_EUCLIDEAN, RULE_SAME_POSITION):
+            raise ValueError(f"unknown connection rule {kind!r}")
+        if not 0 <= int(extent) < 2 ** 32 or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("extent is a uint32, seed a uint64")
+        if probability != probability:
+            raise ValueError("probability is NaN")
+        self.kind, self.extent, self.self_edges = int(kind), int(extent), bool(self_edges)
+        self.probability, self.seed = float(probability), int(seed)
+
+    @classmethod
+    def all_to_all(cls, **kw):
+        return cls(RULE_ALL, **kw)
+
+    @classmethod
+    def chebyshev(cls, r, **kw):
+        return cls(RULE_CHEBYSHEV, extent=r, **kw)
+
+    @classmethod
+    def euclidean(cls, r_squared, **kw):
+        return cls(RULE_EUCLIDEAN, extent=r_squared, **kw)
+
+    @classmethod
+    def same_position(cls, **kw):
+        return cls(RULE_SAME_POSITION, **kw)
+
+    def __repr__(self):
+        return (f"ConnectionRule(kind={self.kind}, extent={self.extent}, self_edges={self.self_edges}, "
+                f"probability={self.probability}, seed={self.seed})")
+
+    def mask(self, pre_shape, post_shape):
+        """bool[n_pre, n_post]: the pairs the device call connects, for grids (rows, cols)"""
+        ra, ca, rb, cb, idx = _pair_grid(pre_shape, post_shape)
+        dr, dc = np.abs(ra - rb), np.abs(ca - cb)
+        on = np.ones(idx.shape, bool)
+        if self.kind == RULE_CHEBYSHEV:
+            on = np.maximum(dr, dc) <= self.extent
+        elif self.kind == RULE_EUCLIDEAN:
+            on = dr * dr + dc * dc <= self.extent
+        elif self.kind == RULE_SAME_POSITION:
+            on = (dr | dc) == 0
+        if not self.self_edges:
+            on = on & ((dr | dc) != 0)
+        p = np.float32(self.probability)
+        if p <= 0:
+            on = np.zeros(idx.shape, bool)
+        elif p < 1:
+            on = on & (_u24(self.seed, idx) < p)
+        return on
+
+
+class WeightRule:
+    """The weight of every pair a ConnectionRule connects: WeightRule.constant(w), or WeightRule.uniform(lo, hi, seed) =
+    lo + (hi - lo) * u24(hash(seed, idx)) in float32 -- synthetic.uniform on the pair index"""
+
+    def __init__(self, kind, lo, hi=0.0, seed=0):
+        if kind not in (WEIGHT_CONSTANT, WEIGHT_UNIFORM):
+            raise ValueError(f"unknown weight rule {kind!r}")
+        if not (np.isfinite(np.float32(lo)) and np.isfinite(np.float32(hi))):
+            raise ValueError("weights must be finite (NaN marks the absent edge)")
+        with np.errstate(over="ignore"):
+            span = np.float32(hi) - np.float32(lo)
+        if kind == WEIGHT_UNIFORM and not np.isfinite(span):
+            raise ValueError("hi - lo overflows float32: the uniform weights would be infinite or NaN")
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("seed is a uint64")
+        self.kind, self.lo, self.hi, self.seed = int(kind), float(lo), float(hi), int(seed)
+
+    @classmethod
+    def constant(cls, w):
+        return cls(WEIGHT_CONSTANT, w)
+
+    @classmethod
+    def uniform(cls, lo, hi, seed=0):
+        return cls(WEIGHT_UNIFORM, lo, hi, seed)
+
+    def __repr__(self):
+        return f"WeightRule(kind={self.kind}, lo={self.lo}, hi={self.hi}, seed={self.seed})"
+
+    def values(self, pre_shape, post_shape):
+        """float32[n_pre, n_post]: the weight the device call gives each pair (whether or not the rule connects it)"""
+        idx = _pair_grid(pre_shape, post_shape)[4]
+        lo, hi = np.float32(self.lo), np.float32(self.hi)
+        if self.kind == WEIGHT_CONSTANT:
+            return np.full(idx.shape, lo, np.float32)
+        return (lo + (hi - lo) * _u24(self.seed, idx)).astype(np.float32)
+
 
 class DeviceNetwork:
     def __init__(self, model=IZHIKEVICH, nt_kinetics=NT_APPROXIMATE, receptor_kinetics=RC_APPROXIMATE,
@@ -190,6 +303,16 @@ class DeviceNetwork:
 
     def fill_graph_synthetic(self, seed, lo, hi, with_diagonal=False):
         self._check(self._L.snn_fill_graph_synthetic(self._h, seed, lo, hi, int(with_diagonal)))
+
+    def connect_by_rule(self, pre_id, post_id, rule, weight=None):
+        """the reference's connect(...) between lattice `pre_id` and neuron lattice `post_id` (the same id: internally), evaluated
+        on the device (snn_connect_by_rule): `rule` a ConnectionRule, `weight` a WeightRule (None: every edge weighs 1).
+        rule.mask / weight.values are the same graph on the host."""
+        weight = WeightRule.constant(1.0) if weight is None else weight
+        if not isinstance(rule, ConnectionRule) or not isinstance(weight, WeightRule):
+            raise TypeError("connect_by_rule takes a ConnectionRule and a WeightRule")
+        self._check(self._L.snn_connect_by_rule(self._h, pre_id, post_id, rule.kind, rule.extent, int(rule.self_edges),
+                                               rule.probability, rule.seed, weight.kind, weight.lo, weight.hi, weight.seed))
 
     # ---- switches -------------------------------------------------------------------------
     def set_synapses(self, electrical=True, chemical=False):
