@@ -213,6 +213,33 @@ int snn_set_graph_csr(snn_network_t *net, const uint64_t *row_ptr, const uint32_
                       const float *weights, uint64_t nnz);
 /* weights in the order they were set (plasticity changes values, never the structure) */
 int snn_get_graph_csr(snn_network_t *net, float *weights, uint64_t nnz);
+/* The structure that goes with those weights, on every sparse handle, whichever call set its graph: the stored edge count, and
+ * row_ptr[n_owned + 1] / pre_index[nnz] in the form snn_set_graph_csr takes (rows = the owned neurons in ascending order).
+ * SNN_ERR_DIM_MISMATCH when nnz is not the stored count.  A handle without a graph reports the empty one. */
+int snn_graph_csr_nnz(snn_network_t *net, uint64_t *nnz);
+int snn_get_graph_csr_structure(snn_network_t *net, uint64_t *row_ptr, uint32_t *pre_index, uint64_t nnz);
+
+/* Connect by rule on SPARSE handles: the CSR graph is built on the device.  A record holds the arguments of snn_connect_by_rule
+ * after the handle, with the same meaning, validation and per-pair formulas (pair index, predicate, draw, weight).  The records
+ * are applied in the order given, as if by successive calls (a later record for the same (pre, post) pair wins), and committed
+ * ONCE: for each record every pair of its block becomes Some(w) or None, every stored edge outside the block survives with the
+ * weight it has on the device NOW (what plasticity made of it, not what was once uploaded); a handle that holds no graph yet
+ * starts from the empty one.  The merged graph -- 12 bytes per edge and 8 per row, nothing of size N^2 anywhere -- is downloaded
+ * once and committed as by snn_set_graph_csr: the edge order of snn_get_graph_csr and of the _csr trace / dw / counter forms is
+ * from then on row by row in ascending presynaptic index (snn_get_graph_csr_structure returns it), and -- UNLIKE the dense form,
+ * which keeps those of the other blocks -- traces, dw and counters of the WHOLE graph restart at 0.
+ * Unsharded sparse handles and contiguous shards (a shard writes the rows it owns).  All or nothing: a record that fails
+ * validation (SNN_ERR_BAD_ARG, the message names "record k: " and the argument), an allocation that fails, or a total of 2^32-1
+ * stored edges or more (SNN_ERR_DIM_MISMATCH; counted in 64 bits before the edges are written) leave the previous graph, its
+ * weights and everything derived from it in place.  Refused with SNN_ERR_BAD_STATE: a dense handle (use snn_connect_by_rule), a
+ * handle that is not finalized, a shard by lattice (range-set ownership: not covered).  n_records == 0 is SNN_OK and changes
+ * nothing; null records with n_records > 0 is SNN_ERR_BAD_ARG. */
+typedef struct snn_connect_record {
+    uint32_t pre_id, post_id, rule, extent;
+    int32_t self_edges; float probability; uint64_t edge_seed;
+    uint32_t weight_rule; float w_lo, w_hi; uint64_t weight_seed;
+} snn_connect_record;
+int snn_connect_by_rules_csr(snn_network_t *net, const snn_connect_record *records, uint32_t n_records);
 
 /* ---- switches (Lattice / LatticeNetwork pub fields, neuron/mod.rs:570-586, 1577-1588) -- */
 

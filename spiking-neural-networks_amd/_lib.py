@@ -135,6 +135,13 @@ class ExchangePlan(C.Structure):
                 ("send_words", C.c_uint64), ("recv_words", C.c_uint64)]
 
 
+class ConnectRecord(C.Structure):
+    """snn_connect_record of include/snn_amd.h (snn_connect_by_rules_csr)"""
+    _fields_ = [("pre_id", C.c_uint32), ("post_id", C.c_uint32), ("rule", C.c_uint32), ("extent", C.c_uint32),
+                ("self_edges", C.c_int32), ("probability", C.c_float), ("edge_seed", C.c_uint64),
+                ("weight_rule", C.c_uint32), ("w_lo", C.c_float), ("w_hi", C.c_float), ("weight_seed", C.c_uint64)]
+
+
 EXCHANGE_ALLGATHER, EXCHANGE_HALO = 0, 1
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)      # snn_exchange_fn(user, hip_stream)
@@ -194,6 +201,9 @@ SIGNATURES = {
     "snn_network_use_csr": (C.c_int, [H, C.c_int]),
     "snn_set_graph_csr": (C.c_int, [H, u64p, u32p, f32p, C.c_uint64]),
     "snn_get_graph_csr": (C.c_int, [H, f32p, C.c_uint64]),
+    "snn_graph_csr_nnz": (C.c_int, [H, u64p]),
+    "snn_get_graph_csr_structure": (C.c_int, [H, u64p, u32p, C.c_uint64]),
+    "snn_connect_by_rules_csr": (C.c_int, [H, C.POINTER(ConnectRecord), C.c_uint32]),
     "snn_set_synapses": (C.c_int, [H, C.c_int, C.c_int]),
     "snn_set_plasticity": (C.c_int, [H, C.c_uint32] + [C.c_float] * 5 + [C.c_int]),
     "snn_set_history": (C.c_int, [H, C.c_int, C.c_int]),

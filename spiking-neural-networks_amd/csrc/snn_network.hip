@@ -326,6 +326,26 @@ int snn_fill_graph_synthetic(snn_network_t *net, uint64_t seed, float lo, float 
 }
 ABI_CATCH
 
+// the arguments of one connection by rule, checked (snn_connect_by_rule; `where` = "record k: " for snn_connect_by_rules_csr)
+static int connect_check(const snn_network *net, const std::string &where, uint32_t pre_id, uint32_t post_id, uint32_t rule, float probability,
+                         uint32_t weight_rule, float w_lo, float w_hi, const LatticeInfo **pre_out, const LatticeInfo **post_out)
+{
+    const LatticeInfo *pre = find_lattice(net, pre_id), *post = find_lattice(net, post_id);
+    if (!pre) return fail(SNN_ERR_BAD_ARG, where + "pre_id: unknown lattice id " + std::to_string(pre_id));
+    if (!post) return fail(SNN_ERR_BAD_ARG, where + "post_id: unknown lattice id " + std::to_string(post_id));
+    if (post->spike_train)   // LatticeNetworkError::PostsynapticLatticeCannotBeSpikeTrain, neuron/mod.rs:1852-1854
+        return fail(SNN_ERR_BAD_ARG, where + "post_id: lattice " + std::to_string(post_id) + " is a spike-train lattice, which is never postsynaptic");
+    if (rule >= CONNECT_RULES) return fail(SNN_ERR_BAD_ARG, where + "rule: unknown connection rule " + std::to_string(rule));
+    if (weight_rule >= CONNECT_WEIGHTS) return fail(SNN_ERR_BAD_ARG, where + "weight_rule: unknown weight rule " + std::to_string(weight_rule));
+    if (probability != probability) return fail(SNN_ERR_BAD_ARG, where + "probability is NaN");
+    if (w_lo - w_lo != 0.0f) return fail(SNN_ERR_BAD_ARG, where + "w_lo is not finite (NaN is the absent-edge sentinel of the device matrix)");
+    if (w_hi - w_hi != 0.0f) return fail(SNN_ERR_BAD_ARG, where + "w_hi is not finite (NaN is the absent-edge sentinel of the device matrix)");
+    if (weight_rule == CONNECT_UNIFORM && (w_hi - w_lo) - (w_hi - w_lo) != 0.0f)      // (lo + inf * u24 is +-inf, or NaN where u24 is 0)
+        return fail(SNN_ERR_BAD_ARG, where + "w_hi - w_lo is not finite: the uniform weights would be infinite or the absent-edge sentinel");
+    *pre_out = pre; *post_out = post;
+    return SNN_OK;
+}
+
 int snn_connect_by_rule(snn_network_t *net, uint32_t pre_id, uint32_t post_id, uint32_t rule, uint32_t extent,
                         int self_edges, float probability, uint64_t edge_seed, uint32_t weight_rule, float w_lo,
                         float w_hi, uint64_t weight_seed) ABI_TRY
@@ -333,18 +353,8 @@ int snn_connect_by_rule(snn_network_t *net, uint32_t pre_id, uint32_t post_id, u
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
     if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
     if (net->csr) return fail(SNN_ERR_BAD_STATE, "connecting by rule is for dense handles only: this handle holds a sparse graph");
-    const LatticeInfo *pre = find_lattice(net, pre_id), *post = find_lattice(net, post_id);
-    if (!pre) return fail(SNN_ERR_BAD_ARG, "pre_id: unknown lattice id " + std::to_string(pre_id));
-    if (!post) return fail(SNN_ERR_BAD_ARG, "post_id: unknown lattice id " + std::to_string(post_id));
-    if (post->spike_train)   // LatticeNetworkError::PostsynapticLatticeCannotBeSpikeTrain, neuron/mod.rs:1852-1854
-        return fail(SNN_ERR_BAD_ARG, "post_id: lattice " + std::to_string(post_id) + " is a spike-train lattice, which is never postsynaptic");
-    if (rule >= CONNECT_RULES) return fail(SNN_ERR_BAD_ARG, "rule: unknown connection rule " + std::to_string(rule));
-    if (weight_rule >= CONNECT_WEIGHTS) return fail(SNN_ERR_BAD_ARG, "weight_rule: unknown weight rule " + std::to_string(weight_rule));
-    if (probability != probability) return fail(SNN_ERR_BAD_ARG, "probability is NaN");
-    if (w_lo - w_lo != 0.0f) return fail(SNN_ERR_BAD_ARG, "w_lo is not finite (NaN is the absent-edge sentinel of the device matrix)");
-    if (w_hi - w_hi != 0.0f) return fail(SNN_ERR_BAD_ARG, "w_hi is not finite (NaN is the absent-edge sentinel of the device matrix)");
-    if (weight_rule == CONNECT_UNIFORM && (w_hi - w_lo) - (w_hi - w_lo) != 0.0f)      // (lo + inf * u24 is +-inf, or NaN where u24 is 0)
-        return fail(SNN_ERR_BAD_ARG, "w_hi - w_lo is not finite: the uniform weights would be infinite or the absent-edge sentinel");
+    const LatticeInfo *pre = nullptr, *post = nullptr;
+    TRY(connect_check(net, "", pre_id, post_id, rule, probability, weight_rule, w_lo, w_hi, &pre, &post));
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
     TRY(end_run(net));                     // a deferred reward-modulated update belongs to the OLD weights: apply it first
     net->cross_checked = false;
@@ -558,6 +568,157 @@ int snn_get_graph_csr(snn_network_t *net, float *weights, uint64_t nnz) ABI_TRY
     HIP_TRY(copy_sync(net, sell.data(), net->csr_w, sell.size() * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
     for (uint64_t e = 0; e < nnz; ++e) weights[e] = sell[net->edge_slot_host[e]];
     return SNN_OK;
+}
+ABI_CATCH
+
+int snn_graph_csr_nnz(snn_network_t *net, uint64_t *nnz) ABI_TRY
+{
+    if (!net || !nnz) return fail(SNN_ERR_BAD_ARG, "null argument");
+    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
+    if (!net->csr) return fail(SNN_ERR_BAD_STATE, "handle holds a dense graph");
+    *nnz = net->nnz;
+    return SNN_OK;
+}
+ABI_CATCH
+
+int snn_get_graph_csr_structure(snn_network_t *net, uint64_t *row_ptr, uint32_t *pre_index, uint64_t nnz) ABI_TRY
+{
+    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
+    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
+    if (!net->csr) return fail(SNN_ERR_BAD_STATE, "handle holds a dense graph");
+    if (nnz != net->nnz) return fail(SNN_ERR_DIM_MISMATCH, "nnz does not match the stored graph");
+    if (!row_ptr || (nnz && !pre_index)) return fail(SNN_ERR_BAD_ARG, "null graph pointer");
+    // rows = the owned neurons in ascending order, as snn_set_graph_csr takes them; the edges of a row are edge_slot_host's
+    const uint32_t n_rows = net->n_owned;
+    row_ptr[0] = 0;
+    if (!net->csr_ptr) {                   // no graph set yet: the empty one
+        for (uint32_t k = 0; k < n_rows; ++k) row_ptr[k + 1] = 0;
+        return SNN_OK;
+    }
+    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
+    TRY(end_run(net));
+    hvec<uint32_t> row_len((size_t)(net->n_loc + 63) / 64 * 64), sell((size_t)net->sell_entries);
+    HIP_TRY(copy_sync(net, row_len.data(), net->csr_row_len, row_len.size() * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    HIP_TRY(copy_sync(net, sell.data(), net->csr_pre, sell.size() * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    for (uint32_t k = 0; k < n_rows; ++k) row_ptr[k + 1] = row_ptr[k] + row_len[net->block_mode ? net->owned_local_host[k] : k];
+    if (row_ptr[n_rows] != nnz) return fail(SNN_ERR_BAD_STATE, "stored row lengths do not add up to the stored edge count");
+    for (uint64_t e = 0; e < nnz; ++e) pre_index[e] = sell[net->edge_slot_host[e]];
+    return SNN_OK;
+}
+ABI_CATCH
+
+int snn_connect_by_rules_csr(snn_network_t *net, const snn_connect_record *records, uint32_t n_records) ABI_TRY
+{
+    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
+    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
+    if (!net->csr) return fail(SNN_ERR_BAD_STATE, "handle holds a dense graph: connect it with snn_connect_by_rule");
+    if (net->block_mode) return fail(SNN_ERR_BAD_STATE, "connecting by rule does not cover shards by lattice (range-set ownership): not covered");
+    if (n_records == 0) return SNN_OK;
+    if (!records) return fail(SNN_ERR_BAD_ARG, "records is null");
+    hvec<std::pair<const LatticeInfo *, const LatticeInfo *>> ends(n_records);
+    for (uint32_t k = 0; k < n_records; ++k) {
+        const snn_connect_record &r = records[k];
+        TRY(connect_check(net, "record " + std::to_string(k) + ": ", r.pre_id, r.post_id, r.rule, r.probability, r.weight_rule, r.w_lo,
+                          r.w_hi, &ends[k].first, &ends[k].second));
+    }
+    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
+    TRY(end_run(net));                     // a deferred update belongs to the weights the merge is about to read
+    const uint32_t n = net->n_loc, scan_blocks = (n + 255u) / 256u;
+    // two sets of working CSR (the merge of a record reads one and writes the other), the row lengths and the scan's words: all
+    // locals, freed on every exit
+    dev_ptr<uint32_t> ptr[2], pre[2], len_d;
+    dev_ptr<float> w[2];
+    dev_ptr<unsigned long long> sums_d;              // [scan_blocks] block sums, then [1] the total
+    auto sized = [&](auto *dst, size_t bytes) -> int {
+        HIP_TRY(snn_malloc(dst, std::max<size_t>(bytes, 256)), SNN_ERR_BUFFER_CREATE);
+        return SNN_OK;
+    };
+    for (int s = 0; s < 2; ++s) TRY(sized(&ptr[s], ((size_t)n + 1) * 4));
+    TRY(sized(&len_d, (size_t)n * 4));
+    TRY(sized(&sums_d, ((size_t)scan_blocks + 1) * 8));
+    unsigned long long *total_d = sums_d.get() + scan_blocks;
+    // lengths -> ptr (n + 1 offsets), the 64-bit total read back
+    auto scan = [&](const uint32_t *len, uint32_t *out, uint64_t *total) -> int {
+        *total = 0;
+        if (n == 0) return hipMemsetAsync(out, 0, 4, net->stream) == hipSuccess ? SNN_OK : fail(SNN_ERR_BUFFER_WRITE, "hipMemsetAsync failed");
+        hipLaunchKernelGGL(k_connect_scan_local, dim3(scan_blocks), dim3(256), 0, net->stream, len, n, out, sums_d.get());
+        hipLaunchKernelGGL(k_connect_scan_sums, dim3(1), dim3(256), 0, net->stream, sums_d.get(), scan_blocks, total_d);
+        hipLaunchKernelGGL(k_connect_scan_add, dim3(scan_blocks), dim3(256), 0, net->stream, out, n, (const unsigned long long *)sums_d.get(),
+                           (const unsigned long long *)total_d);
+        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+        unsigned long long t = 0;
+        HIP_TRY(copy_sync(net, &t, total_d, 8, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+        *total = t;
+        return SNN_OK;
+    };
+    // ---- the current graph, from SELL-64 (weights as plasticity left them) ----
+    int cur = 0;
+    uint64_t nnz = 0;
+    if (net->csr_ptr && n) {
+        TRY(scan(net->csr_row_len, ptr[cur], &nnz));
+        if (nnz != net->nnz) return fail(SNN_ERR_BAD_STATE, "stored row lengths do not add up to the stored edge count");
+        TRY(sized(&pre[cur], nnz * 4));
+        TRY(sized(&w[cur], nnz * 4));
+        hipLaunchKernelGGL(k_connect_csr_export, dim3(scan_blocks), dim3(256), 0, net->stream, (const uint32_t *)net->csr_ptr,
+                           (const uint32_t *)net->csr_pre, (const float *)net->csr_w, (const uint32_t *)net->csr_row_len,
+                           (const uint32_t *)ptr[cur], n, pre[cur].get(), w[cur].get());
+        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+    } else {
+        HIP_TRY(hipMemsetAsync(ptr[cur], 0, ((size_t)n + 1) * 4, net->stream), SNN_ERR_BUFFER_WRITE);
+        TRY(sized(&pre[cur], 0));
+        TRY(sized(&w[cur], 0));
+    }
+    // ---- record by record: count, scan, check the total, fill, swap ----
+    for (uint32_t k = 0; k < n_records; ++k) {
+        const snn_connect_record &r = records[k];
+        const LatticeInfo *lp = ends[k].first, *lq = ends[k].second;
+        // the block's rows this handle owns, as local rows (the dense form: its columns)
+        const uint32_t c_begin = std::max(lq->first, net->q0), c_end = std::min(lq->first + lq->count, net->q0 + n);
+        if (!n || c_begin >= c_end) continue;          // (an empty pre lattice still clears nothing: the block has no pair)
+        if (!lp->count) continue;
+        ConnectCsrArgs a{};
+        a.c.col0 = c_begin - net->q0; a.c.n_cols = c_end - c_begin; a.c.post_i0 = c_begin - lq->first;
+        a.c.post_cols = lq->cols; a.c.post_count = lq->count;
+        a.c.pre_first = lp->first; a.c.pre_count = lp->count; a.c.pre_rows = lp->rows; a.c.pre_cols = lp->cols;
+        a.c.extent = r.extent; a.c.probability = r.probability; a.c.edge_seed = r.edge_seed; a.c.weight_seed = r.weight_seed;
+        a.c.w_lo = r.w_lo; a.c.w_hi = r.w_hi;
+        a.n_rows = n;
+        a.window = connect_window_extent(r.rule, r.extent, std::max(std::max(lp->rows, lp->cols), std::max(lq->rows, lq->cols)));
+        a.old_ptr = ptr[cur]; a.old_pre = pre[cur]; a.old_w = w[cur];
+        a.new_len = len_d;
+        const bool thin = r.probability < 1.0f, self = r.self_edges != 0;
+        const dim3 grid(std::min<uint32_t>((n + 3u) / 4u, 16384u));
+        hipLaunchKernelGGL(connect_csr_kernel<false>((int)r.rule, (int)r.weight_rule, thin, self), grid, dim3(256), 0, net->stream, a);
+        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+        uint64_t total = 0;
+        TRY(scan(len_d, ptr[cur ^ 1], &total));
+        if (total >= 0xFFFFFFFFull)
+            return fail(SNN_ERR_DIM_MISMATCH, "record " + std::to_string(k) + ": the graph would hold " + std::to_string(total) +
+                                                  " stored synapses, more than 2^32-2 per handle");
+        TRY(sized(&pre[cur ^ 1], total * 4));
+        TRY(sized(&w[cur ^ 1], total * 4));
+        a.new_ptr = ptr[cur ^ 1]; a.new_pre = pre[cur ^ 1]; a.new_w = w[cur ^ 1];
+        hipLaunchKernelGGL(connect_csr_kernel<true>((int)r.rule, (int)r.weight_rule, thin, self), grid, dim3(256), 0, net->stream, a);
+        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+        HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);      // (the set just read is freed when it is next sized)
+        cur ^= 1;
+        nnz = total;
+    }
+    // ---- one download, then the host builder of snn_set_graph_csr: all or nothing from here as before here ----
+    hvec<uint32_t> ptr32((size_t)n + 1), pre_h((size_t)nnz);
+    hvec<float> w_h((size_t)nnz);
+    HIP_TRY(copy_sync(net, ptr32.data(), ptr[cur], ptr32.size() * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    if (nnz) {
+        HIP_TRY(copy_sync(net, pre_h.data(), pre[cur], nnz * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+        HIP_TRY(copy_sync(net, w_h.data(), w[cur], nnz * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    }
+    for (int s = 0; s < 2; ++s) { ptr[s].reset(); pre[s].reset(); w[s].reset(); }      // (the commit peaks at old graph + new graph)
+    len_d.reset(); sums_d.reset();
+    hvec<uint64_t> ptr64(ptr32.begin(), ptr32.end());
+    hvec<uint32_t>().swap(ptr32);
+    uint32_t no_pre = 0;
+    float no_w = 0.0f;
+    return set_graph_csr_impl(net, ptr64.data(), nnz ? pre_h.data() : &no_pre, nnz ? w_h.data() : &no_w, nnz);
 }
 ABI_CATCH
 

@@ -567,10 +567,26 @@ public:
     static LatticeNetworkGPU from_network(const LatticeNetwork<T, S> &net, int nt_kinetics = SNN_NT_APPROXIMATE,
                                           int receptor_kinetics = SNN_RC_APPROXIMATE, int device = 0)
     {
+        return create(net, nt_kinetics, receptor_kinetics, device, false);
+    }
+    // The same network on a SPARSE handle (snn_network_use_csr): the graph is held as CSR on the device, for networks whose
+    // N x N matrix cannot exist.  The host copy's edges are uploaded once; from then on the graph lives on the device only
+    // (connect_sparse, csr_structure, csr_weights) -- run_lattices / sync refresh the cells and histories, not the matrices.
+    static LatticeNetworkGPU from_network_sparse(const LatticeNetwork<T, S> &net, int nt_kinetics = SNN_NT_APPROXIMATE,
+                                                 int receptor_kinetics = SNN_RC_APPROXIMATE, int device = 0)
+    {
+        return create(net, nt_kinetics, receptor_kinetics, device, true);
+    }
+
+  private:
+    static LatticeNetworkGPU create(const LatticeNetwork<T, S> &net, int nt_kinetics, int receptor_kinetics, int device, bool sparse)
+    {
         LatticeNetworkGPU g;
         g.network = net;
+        g.sparse_ = sparse;
         const int st = net.spike_train_lattices.empty() ? SNN_ST_NONE : S::MODEL;
         check(snn_network_create(device, T::MODEL, nt_kinetics, receptor_kinetics, st, &g.h_));
+        if (sparse) check(snn_network_use_csr(g.h_, 1));
         for (const auto &[id, l] : net.lattices) check(snn_network_add_lattice(g.h_, (uint32_t)id, (uint32_t)l.rows(), (uint32_t)l.cols()));
         for (const auto &[id, l] : net.spike_train_lattices)
             check(snn_network_add_spike_train_lattice(g.h_, (uint32_t)id, (uint32_t)l.rows(), (uint32_t)l.cols()));
@@ -582,11 +598,13 @@ public:
         for (const auto &[id, l] : net.spike_train_lattices) check(snn_set_spike_train_clock(g.h_, (uint32_t)id, (uint64_t)l.internal_clock));
         return g;
     }
+
+  public:
     LatticeNetworkGPU() = default;
     LatticeNetworkGPU(LatticeNetworkGPU &&o) noexcept { *this = std::move(o); }
     LatticeNetworkGPU &operator=(LatticeNetworkGPU &&o) noexcept
     {
-        if (this != &o) { release(); h_ = o.h_; o.h_ = nullptr; network = std::move(o.network); grid_history = std::move(o.grid_history); }
+        if (this != &o) { release(); h_ = o.h_; o.h_ = nullptr; sparse_ = o.sparse_; network = std::move(o.network); grid_history = std::move(o.grid_history); }
         return *this;
     }
     LatticeNetworkGPU(const LatticeNetworkGPU &) = delete;
@@ -615,6 +633,32 @@ public:
     {
         check(snn_connect_by_rule(h_, (uint32_t)pre, (uint32_t)post, rule, extent, self_edges, probability, edge_seed, weight_rule,
                                   w_lo, w_hi, weight_seed));
+    }
+
+    // The same on a sparse handle (from_network_sparse), snn_connect_by_rules_csr: the records are applied in order and committed
+    // once; edges outside their blocks keep their current weights, traces / dw / counters of the whole graph restart at 0.
+    void connect_sparse(const std::vector<snn_connect_record> &records)
+    {
+        check(snn_connect_by_rules_csr(h_, records.data(), (uint32_t)records.size()));
+    }
+    // (row_ptr, pre_index) of a sparse handle's graph, rows = neurons in ascending index; csr_weights() in the same edge order
+    std::pair<std::vector<uint64_t>, std::vector<uint32_t>> csr_structure()
+    {
+        uint64_t nnz = 0;
+        uint32_t nn = 0;
+        check(snn_graph_csr_nnz(h_, &nnz));
+        check(snn_network_sizes(h_, &nn, nullptr, nullptr, nullptr));
+        std::pair<std::vector<uint64_t>, std::vector<uint32_t>> out{std::vector<uint64_t>((size_t)nn + 1), std::vector<uint32_t>(nnz)};
+        check(snn_get_graph_csr_structure(h_, out.first.data(), out.second.data(), nnz));
+        return out;
+    }
+    std::vector<float> csr_weights()
+    {
+        uint64_t nnz = 0;
+        check(snn_graph_csr_nnz(h_, &nnz));
+        std::vector<float> w(nnz);
+        check(snn_get_graph_csr(h_, w.data(), nnz));
+        return w;
     }
 
   private:
@@ -717,6 +761,7 @@ public:
 
 private:
     snn_network_t *h_ = nullptr;
+    bool sparse_ = false;
     void release() { if (h_) { snn_network_destroy(h_); h_ = nullptr; } }
 
     std::vector<float> reduced(size_t id, bool eeg)
@@ -740,6 +785,7 @@ private:
         }
         for (const auto &[id, l] : network.spike_train_lattices) detail::upload_cells<S>(h_, (uint32_t)id, l.cell_grid);
         if (nt == 0 || nn == 0) return;
+        if (sparse_) { upload_sparse(nn); return; }
         // InterleavingGraphGPU::convert_to_gpu (graph/mod.rs:644-807): internal graphs + connecting graph
         std::vector<float> w(nt * nn, 0.0f);
         std::vector<uint32_t> c(nt * nn, 0);
@@ -770,6 +816,41 @@ private:
         check(snn_set_graph_rows(h_, 0, (uint32_t)nt, w.data(), c.data()));
     }
 
+    // the host copy's edges as CSR by postsynaptic neuron (ascending presynaptic index per row)
+    void upload_sparse(uint32_t nn)
+    {
+        std::vector<std::map<uint32_t, float>> rows(nn);
+        for (const auto &[id, l] : network.lattices) {
+            uint32_t first = 0, count = 0;
+            check(snn_network_lattice_range(h_, (uint32_t)id, &first, &count));
+            const size_t cols = l.cols();
+            for (size_t i = 0; i < l.graph.matrix.size(); ++i)
+                for (size_t j = 0; j < l.graph.matrix[i].size(); ++j)
+                    if (l.graph.matrix[i][j]) {
+                        const Position pi = l.graph.index_to_position[i], pj = l.graph.index_to_position[j];
+                        rows[first + pj.first * cols + pj.second][(uint32_t)(first + pi.first * cols + pi.second)] = *l.graph.matrix[i][j];
+                    }
+        }
+        for (const auto &[pre, post, weight] : network.connecting_edges) {
+            uint32_t f0 = 0, c0 = 0, f1 = 0, c1 = 0;
+            check(snn_network_lattice_range(h_, (uint32_t)pre.id, &f0, &c0));
+            check(snn_network_lattice_range(h_, (uint32_t)post.id, &f1, &c1));
+            const size_t pc = network.lattices.count(pre.id) ? network.lattices.at(pre.id).cols()
+                                                             : network.spike_train_lattices.at(pre.id).cols();
+            const size_t qc = network.lattices.at(post.id).cols();
+            rows[f1 + post.pos.first * qc + post.pos.second][(uint32_t)(f0 + pre.pos.first * pc + pre.pos.second)] = weight;
+        }
+        std::vector<uint64_t> ptr(1, 0);
+        std::vector<uint32_t> pre_index;
+        std::vector<float> w;
+        for (const auto &row : rows) {
+            for (const auto &[p, x] : row) { pre_index.push_back(p); w.push_back(x); }
+            ptr.push_back(pre_index.size());
+        }
+        if (pre_index.empty()) return;            // (a handle without a graph holds the empty one)
+        check(snn_set_graph_csr(h_, ptr.data(), pre_index.data(), w.data(), pre_index.size()));
+    }
+
     void download()
     {
         uint64_t clock = 0, steps = 0;
@@ -781,7 +862,7 @@ private:
         const size_t nt = (size_t)nn + nc;
         std::vector<float> w;
         std::vector<uint32_t> c;
-        if (nt && nn) {
+        if (nt && nn && !sparse_) {
             w.resize(nt * nn); c.resize(nt * nn);
             check(snn_get_graph_rows(h_, 0, (uint32_t)nt, w.data(), c.data()));
         }
@@ -791,7 +872,7 @@ private:
             uint32_t first = 0, count = 0;
             check(snn_network_lattice_range(h_, (uint32_t)id, &first, &count));
             const size_t cols = l.cols();
-            for (size_t i = 0; i < l.graph.matrix.size(); ++i)          // weights back into the AdjacencyMatrix
+            for (size_t i = 0; i < (sparse_ ? 0 : l.graph.matrix.size()); ++i)          // weights back into the AdjacencyMatrix
                 for (size_t j = 0; j < l.graph.matrix[i].size(); ++j) {
                     const Position pi = l.graph.index_to_position[i], pj = l.graph.index_to_position[j];
                     const size_t gi = first + pi.first * cols + pi.second, gj = first + pj.first * cols + pj.second;
@@ -808,6 +889,7 @@ private:
             }
         }
         for (auto &e : network.connecting_edges) {
+            if (sparse_) break;                   // (the graph of a sparse mirror stays on the device)
             auto &[pre, post, weight] = e;
             uint32_t f0 = 0, c0 = 0, f1 = 0, c1 = 0;
             check(snn_network_lattice_range(h_, (uint32_t)pre.id, &f0, &c0));

@@ -314,6 +314,35 @@ class DeviceNetwork:
         self._check(self._L.snn_connect_by_rule(self._h, pre_id, post_id, rule.kind, rule.extent, int(rule.self_edges),
                                                rule.probability, rule.seed, weight.kind, weight.lo, weight.hi, weight.seed))
 
+    def connect_sparse(self, plan):
+        """connect(...) on a sparse handle, the graph merged on the device (snn_connect_by_rules_csr): `plan` is a list of
+        (pre_id, post_id, ConnectionRule, WeightRule or None), applied in order and committed once.  Every edge outside the plan's
+        blocks keeps its current weight; traces, dw and counters of the whole graph restart at 0.  The committed edge order is
+        graph_csr_structure()'s."""
+        records = (_lib.ConnectRecord * max(len(plan), 1))()
+        for k, entry in enumerate(plan):
+            if not isinstance(entry, (tuple, list)) or len(entry) != 4:
+                raise TypeError(f"plan[{k}] must be (pre_id, post_id, ConnectionRule, WeightRule or None)")
+            pre_id, post_id, rule, weight = entry
+            weight = WeightRule.constant(1.0) if weight is None else weight
+            if not isinstance(rule, ConnectionRule) or not isinstance(weight, WeightRule):
+                raise TypeError(f"plan[{k}]: connect_sparse takes a ConnectionRule and a WeightRule")
+            records[k] = _lib.ConnectRecord(int(pre_id), int(post_id), rule.kind, rule.extent, int(rule.self_edges), rule.probability,
+                                            rule.seed, weight.kind, weight.lo, weight.hi, weight.seed)
+        self._check(self._L.snn_connect_by_rules_csr(self._h, records, len(plan)))
+        nnz = C.c_uint64()
+        self._check(self._L.snn_graph_csr_nnz(self._h, C.byref(nnz)))
+        self._nnz = int(nnz.value)
+
+    def graph_csr_structure(self):
+        """(row_ptr uint64[n_owned + 1], pre_index uint32[nnz]) of a sparse handle: the edge order of get_graph_csr"""
+        nnz = C.c_uint64()
+        self._check(self._L.snn_graph_csr_nnz(self._h, C.byref(nnz)))
+        rp = _out(sum(e - b for b, e in self.ranges) + 1, np.uint64)
+        pi = _out(int(nnz.value), np.uint32)
+        self._check(self._L.snn_get_graph_csr_structure(self._h, rp.ctypes.data_as(_lib.u64p), pi.ctypes.data_as(_lib.u32p), pi.size))
+        return rp, pi
+
     # ---- switches -------------------------------------------------------------------------
     def set_synapses(self, electrical=True, chemical=False):
         self._check(self._L.snn_set_synapses(self._h, int(electrical), int(chemical)))
