@@ -201,6 +201,34 @@ int snn_connect_by_rule(snn_network_t *net, uint32_t pre_id, uint32_t post_id, u
                         int self_edges, float probability, uint64_t edge_seed, uint32_t weight_rule, float w_lo,
                         float w_hi, uint64_t weight_seed);
 
+/* The Graph trait on a dense handle (graph/mod.rs:42-72: lookup_weight, edit_weight, get_incoming_connections,
+ * get_outgoing_connections) without moving rows: single elements, one column, one row.  Indices are interleaved global
+ * indices, pre < n_tot, post < n_neurons.  For every element the four calls agree bit for bit with what snn_get_graph_rows
+ * returns at that moment (deferred plasticity updates are applied first); after snn_graph_edit, snn_get_graph_rows returns the
+ * edited values and nothing else has changed.
+ *   snn_graph_lookup    lookup_weight for n pairs: connected[k] = 1 and weights[k] = w for Some(w); 0 and 0.0f for None.
+ *   snn_graph_edit      edit_weight for n pairs: connected[k] != 0 -> Some(weights[k]), else None (weights[k] is then not read
+ *                       as a weight).  The pairs are applied as if one after another: of a pair listed more than once the last
+ *                       occurrence wins.  A connected pair whose weight is NaN is SNN_ERR_BAD_ARG (NaN is the absent-edge
+ *                       sentinel, as for snn_set_graph_rows) -- found before anything changes.  Traces, dw and counters of the
+ *                       edited pairs (reward-modulated handles, connection kinds) restart at 0; those of all others stay.
+ *   snn_graph_incoming  the presynaptic indices of the edges into `post` with their weights, in ASCENDING index order;
+ *   snn_graph_outgoing  the postsynaptic indices of the edges out of `pre` likewise.  *count is always set; the lists are written
+ *                       only when capacity >= *count, otherwise the call returns SNN_OK with nothing written (the two-call idiom of
+ *                       snn_halo_needs).  With *count == 0 the list pointers may be null.
+ * A shard handle answers for the columns it owns, [post_begin, post_end): a pair, or the `post` of snn_graph_incoming, outside
+ * them is SNN_ERR_BAD_ARG; snn_graph_outgoing lists the owned columns only.  pre >= n_tot or post >= n_neurons is
+ * SNN_ERR_BAD_ARG.  Every pair of a call is validated before anything is read or written and snn_last_error names the first
+ * offending pair by its position in the call: a refused snn_graph_edit leaves the graph as it was.  n == 0 is SNN_OK and touches
+ * nothing; null pointers with n > 0 are SNN_ERR_BAD_ARG.  A handle that is not finalized, or holds a sparse graph -- its
+ * structure is fixed and its host form is 12 bytes per edge: snn_get_graph_csr_structure / snn_get_graph_csr -- is
+ * SNN_ERR_BAD_STATE. */
+int snn_graph_lookup(snn_network_t *net, const uint32_t *pre, const uint32_t *post, size_t n, float *weights, uint8_t *connected);
+int snn_graph_edit(snn_network_t *net, const uint32_t *pre, const uint32_t *post, const float *weights, const uint8_t *connected,
+                   size_t n);
+int snn_graph_incoming(snn_network_t *net, uint32_t post, uint32_t *pre_index, float *weights, uint64_t capacity, uint64_t *count);
+int snn_graph_outgoing(snn_network_t *net, uint32_t pre, uint32_t *post_index, float *weights, uint64_t capacity, uint64_t *count);
+
 /* Sparse form, CSR by LOCAL postsynaptic neuron (the reference's sparse graph, AdjacencyList
  * graph/mod.rs:974-1118, has no GPU form; needed where a dense N x N matrix cannot exist, e.g.
  * BASELINE configs[4]).  snn_network_use_csr must precede finalize; a handle is dense or CSR for life.

@@ -198,6 +198,10 @@ SIGNATURES = {
     "snn_fill_graph_synthetic": (C.c_int, [H, C.c_uint64, C.c_float, C.c_float, C.c_int]),
     "snn_connect_by_rule": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_uint64,
                                       C.c_uint32, C.c_float, C.c_float, C.c_uint64]),
+    "snn_graph_lookup": (C.c_int, [H, u32p, u32p, C.c_size_t, f32p, u8p]),
+    "snn_graph_edit": (C.c_int, [H, u32p, u32p, f32p, u8p, C.c_size_t]),
+    "snn_graph_incoming": (C.c_int, [H, C.c_uint32, u32p, f32p, C.c_uint64, u64p]),
+    "snn_graph_outgoing": (C.c_int, [H, C.c_uint32, u32p, f32p, C.c_uint64, u64p]),
     "snn_network_use_csr": (C.c_int, [H, C.c_int]),
     "snn_set_graph_csr": (C.c_int, [H, u64p, u32p, f32p, C.c_uint64]),
     "snn_get_graph_csr": (C.c_int, [H, f32p, C.c_uint64]),

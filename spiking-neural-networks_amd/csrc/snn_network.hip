@@ -389,6 +389,174 @@ int snn_connect_by_rule(snn_network_t *net, uint32_t pre_id, uint32_t post_id, u
 }
 ABI_CATCH
 
+// ---- the Graph trait on a dense handle (graph/mod.rs:42-72): lookup_weight, edit_weight, incoming / outgoing connections ----
+// what the four calls check first, as graph_rows_io does
+static int graph_query_begin(const snn_network *net)
+{
+    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
+    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
+    if (net->csr)
+        return fail(SNN_ERR_BAD_STATE, "handle holds a CSR graph, whose structure is fixed: read it with snn_get_graph_csr_structure / "
+                                       "snn_get_graph_csr (12 bytes per edge on the host)");
+    return SNN_OK;
+}
+// one index pair of a call: inside the matrix, and in a column this handle owns (`what`: "pair k" / "post")
+static int graph_pair_check(const snn_network *net, const std::string &what, uint32_t pre, uint32_t post)
+{
+    const std::string where = what + " (pre " + std::to_string(pre) + ", post " + std::to_string(post) + "): ";
+    if (pre >= net->n_tot) return fail(SNN_ERR_BAD_ARG, where + "pre is not below n_tot = " + std::to_string(net->n_tot));
+    if (post >= net->nn) return fail(SNN_ERR_BAD_ARG, where + "post is not below n_neurons = " + std::to_string(net->nn));
+    if (post < net->q0 || post >= net->q0 + net->n_loc)
+        return fail(SNN_ERR_BAD_ARG, where + "post is outside the columns this shard owns, [" + std::to_string(net->q0) + ", " +
+                                     std::to_string(net->q0 + net->n_loc) + ")");
+    return SNN_OK;
+}
+constexpr size_t GRAPH_PAIRS_HOP = (size_t)1 << 20;         // pairs per launch: the device lists of a call hold no more
+
+int snn_graph_lookup(snn_network_t *net, const uint32_t *pre, const uint32_t *post, size_t n, float *weights, uint8_t *connected) ABI_TRY
+{
+    TRY(graph_query_begin(net));
+    if (n == 0) return SNN_OK;
+    if (!pre || !post || !weights || !connected) return fail(SNN_ERR_BAD_ARG, "null pointer with n > 0");
+    for (size_t k = 0; k < n; ++k)
+        if (pre[k] >= net->n_tot || post[k] - net->q0 >= net->n_loc) return graph_pair_check(net, "pair " + std::to_string(k), pre[k], post[k]);
+    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
+    TRY(end_run(net));                     // deferred STDP / R-STDP updates belong to the weights a lookup sees
+    const size_t hop = std::min(n, GRAPH_PAIRS_HOP);
+    dev_ptr<uint32_t> pre_d, post_d;
+    dev_ptr<float> w_d;
+    dev_ptr<uint8_t> c_d;
+    HIP_TRY(snn_malloc(&pre_d, hop * 4), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(&post_d, hop * 4), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(&w_d, hop * 4), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(&c_d, std::max<size_t>(hop, 256)), SNN_ERR_BUFFER_CREATE);
+    for (size_t k = 0; k < n; k += hop) {
+        const uint32_t m = (uint32_t)std::min(hop, n - k);
+        HIP_TRY(copy_sync(net, pre_d, pre + k, (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        HIP_TRY(copy_sync(net, post_d, post + k, (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        hipLaunchKernelGGL(k_graph_lookup, dim3((m + 255u) / 256u), dim3(256), 0, net->stream, net->W, net->ld, net->q0, pre_d, post_d, m,
+                           w_d, c_d);
+        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+        HIP_TRY(copy_sync(net, weights + k, w_d, (size_t)m * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+        HIP_TRY(copy_sync(net, connected + k, c_d, m, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    }
+    return SNN_OK;
+}
+ABI_CATCH
+
+int snn_graph_edit(snn_network_t *net, const uint32_t *pre, const uint32_t *post, const float *weights, const uint8_t *connected,
+                   size_t n) ABI_TRY
+{
+    TRY(graph_query_begin(net));
+    if (n == 0) return SNN_OK;
+    if (!pre || !post || !weights || !connected) return fail(SNN_ERR_BAD_ARG, "null pointer with n > 0");
+    // every pair is checked before anything is written: a refused call leaves the graph as it was
+    bool ascending = true;                 // strictly, by (pre, post): no pair twice
+    for (size_t k = 0; k < n; ++k) {
+        if (pre[k] >= net->n_tot || post[k] - net->q0 >= net->n_loc) return graph_pair_check(net, "pair " + std::to_string(k), pre[k], post[k]);
+        if (connected[k] && weights[k] != weights[k])
+            return fail(SNN_ERR_BAD_ARG, "pair " + std::to_string(k) + " (pre " + std::to_string(pre[k]) + ", post " + std::to_string(post[k]) +
+                                         "): a connected edge carries a NaN weight; NaN is the absent-edge sentinel of the device matrix, such "
+                                         "an edge cannot be stored (graph/mod.rs:204-213).  Nothing of this call was applied");
+        if (k && (pre[k] < pre[k - 1] || (pre[k] == pre[k - 1] && post[k] <= post[k - 1]))) ascending = false;
+    }
+    // "as if one after another": of a pair that occurs more than once the LAST occurrence is kept, decided here -- every element is
+    // written by one thread, whatever the order the threads run in
+    hvec<uint64_t> order;
+    size_t kept = n;
+    if (!ascending) {
+        order.resize(n);
+        for (size_t k = 0; k < n; ++k) order[k] = k;
+        auto key = [&](uint64_t k) { return ((uint64_t)pre[k] << 32) | post[k]; };
+        std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return key(a) != key(b) ? key(a) < key(b) : a < b; });
+        kept = 0;
+        for (size_t k = 0; k < n; ++k)
+            if (k + 1 == n || key(order[k + 1]) != key(order[k])) order[kept++] = order[k];
+    }
+    const size_t hop = std::min(kept, GRAPH_PAIRS_HOP);
+    hvec<uint32_t> pre_h(hop), post_h(hop);
+    hvec<float> value_h(hop);
+    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
+    TRY(end_run(net));                     // a deferred update belongs to the OLD weights: applied now, it cannot overwrite the edit
+    dev_ptr<uint32_t> pre_d, post_d;
+    dev_ptr<float> value_d;
+    HIP_TRY(snn_malloc(&pre_d, hop * 4), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(&post_d, hop * 4), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(&value_d, hop * 4), SNN_ERR_BUFFER_CREATE);
+    if (net->opt.pinned_copies && !net->copy_stage)           // (the staging buffer of copy_sync: allocated before the first write)
+        HIP_TRY(host_malloc(&net->copy_stage, (size_t)8 << 20, hipHostMallocDefault), SNN_ERR_BUFFER_CREATE);
+    net->cross_checked = false;
+    net->cache.counts_dirty = true;        // stale from here on, whichever way the call ends
+    w24_invalidate(net);
+    const float absent = std::nanf("");
+    for (size_t k = 0; k < kept; k += hop) {
+        const uint32_t m = (uint32_t)std::min(hop, kept - k);
+        for (uint32_t j = 0; j < m; ++j) {
+            const size_t src = ascending ? k + j : (size_t)order[k + j];
+            pre_h[j] = pre[src]; post_h[j] = post[src];
+            value_h[j] = connected[src] ? weights[src] : absent;
+        }
+        HIP_TRY(copy_sync(net, pre_d, pre_h.data(), (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        HIP_TRY(copy_sync(net, post_d, post_h.data(), (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        HIP_TRY(copy_sync(net, value_d, value_h.data(), (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        hipLaunchKernelGGL(k_graph_edit, dim3((m + 255u) / 256u), dim3(256), 0, net->stream, net->W, net->trace.get(), net->pending.get(),
+                           net->edge_counter.get(), net->ld, net->q0, pre_d, post_d, value_d, m);
+        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+        HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
+    }
+    return SNN_OK;
+}
+ABI_CATCH
+
+// one column (incoming) or one row (outgoing) of W as ascending (index, weight) lists: the two-call idiom of snn_halo_needs
+static int graph_line(snn_network *net, bool column, uint32_t line, uint32_t *index, float *weights, uint64_t capacity, uint64_t *count)
+{
+    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
+    TRY(end_run(net));
+    const uint32_t n = column ? net->n_tot : net->n_loc;
+    if (n == 0 || net->n_loc == 0) return SNN_OK;
+    const uint32_t room = index && weights ? (uint32_t)std::min<uint64_t>(capacity, n) : 0u;
+    dev_ptr<uint32_t> index_d, count_d;
+    dev_ptr<float> w_d;
+    HIP_TRY(snn_malloc(&index_d, std::max<size_t>((size_t)room * 4, 256)), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(&w_d, std::max<size_t>((size_t)room * 4, 256)), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(&count_d, 256), SNN_ERR_BUFFER_CREATE);
+    hipLaunchKernelGGL(column ? k_graph_line<true> : k_graph_line<false>, dim3(1), dim3(256), 0, net->stream, net->W, net->ld, net->q0, line, n,
+                       index_d, w_d, room, count_d);
+    HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+    uint32_t found = 0;
+    HIP_TRY(copy_sync(net, &found, count_d, 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    *count = found;
+    if (found == 0 || found > capacity) return SNN_OK;
+    if (!index || !weights) return fail(SNN_ERR_BAD_ARG, "null list pointer with capacity >= count > 0");
+    HIP_TRY(copy_sync(net, index, index_d, (size_t)found * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    HIP_TRY(copy_sync(net, weights, w_d, (size_t)found * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    return SNN_OK;
+}
+
+int snn_graph_incoming(snn_network_t *net, uint32_t post, uint32_t *pre_index, float *weights, uint64_t capacity, uint64_t *count) ABI_TRY
+{
+    TRY(graph_query_begin(net));
+    if (!count) return fail(SNN_ERR_BAD_ARG, "count is null");
+    *count = 0;
+    if (post >= net->nn) return fail(SNN_ERR_BAD_ARG, "post " + std::to_string(post) + " is not below n_neurons = " + std::to_string(net->nn));
+    if (post < net->q0 || post >= net->q0 + net->n_loc)
+        return fail(SNN_ERR_BAD_ARG, "post " + std::to_string(post) + " is outside the columns this shard owns, [" + std::to_string(net->q0) +
+                                     ", " + std::to_string(net->q0 + net->n_loc) + ")");
+    return graph_line(net, true, post - net->q0, pre_index, weights, capacity, count);
+}
+ABI_CATCH
+
+int snn_graph_outgoing(snn_network_t *net, uint32_t pre, uint32_t *post_index, float *weights, uint64_t capacity, uint64_t *count) ABI_TRY
+{
+    TRY(graph_query_begin(net));
+    if (!count) return fail(SNN_ERR_BAD_ARG, "count is null");
+    *count = 0;
+    if (pre >= net->n_tot) return fail(SNN_ERR_BAD_ARG, "pre " + std::to_string(pre) + " is not below n_tot = " + std::to_string(net->n_tot));
+    return graph_line(net, false, pre, post_index, weights, capacity, count);
+}
+ABI_CATCH
+
 int snn_network_use_csr(snn_network_t *net, int enable) ABI_TRY
 {
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");

@@ -25,6 +25,7 @@
 #include "snn_kernels_csr.hpp"
 #include "snn_kernels_dense_step.hpp"
 #include "snn_kernels_exchange.hpp"
+#include "snn_kernels_graph_query.hpp"
 #include "snn_kernels_inputs.hpp"
 #include "snn_kernels_misc.hpp"
 #include "snn_kernels_resident.hpp"
@@ -1131,6 +1132,9 @@ int build_state(snn_network *net)
     // graph + partials + counts
     if (net->csr) net->n_chunks = 1;     // the CSR kernel writes the finished two-level sum
     TRY(dev_alloc_t(net, &net->W, net->csr ? 0 : wcount(net->n_tot, net->ld)));
+    // a fresh dense handle holds NO edge -- padding rows, padding columns and slack included -- not what the allocator handed out:
+    // a graph built block by block (snn_connect_by_rule, snn_graph_edit) never writes the blocks it does not name
+    if (!net->csr) TRY(fill_f32(net, net->W, wcount(net->n_tot, net->ld), std::nanf("")));
     TRY(dev_alloc_t(net, &net->part_i, (size_t)net->n_chunks * net->ld));
     TRY(dev_alloc_t(net, &net->part_t, (size_t)K_TYPES * net->n_chunks * net->ld));
     TRY(dev_alloc_t(net, &net->n_in, net->ld));

@@ -635,6 +635,25 @@ public:
                                   w_lo, w_hi, weight_seed));
     }
 
+    // The Graph trait on the device matrix (graph/mod.rs:42-72) by interleaved global index, dense handles: snn_graph_lookup /
+    // snn_graph_edit for one pair, snn_graph_incoming / snn_graph_outgoing as ascending (index, weight) lists.  Edits change the
+    // device only; sync() brings them into `network`.
+    std::optional<float> lookup_weight(uint32_t pre, uint32_t post)
+    {
+        float w = 0.0f;
+        uint8_t on = 0;
+        check(snn_graph_lookup(h_, &pre, &post, 1, &w, &on));
+        return on ? std::optional<float>(w) : std::nullopt;
+    }
+    void edit_weight(uint32_t pre, uint32_t post, std::optional<float> weight)
+    {
+        const float w = weight.value_or(0.0f);
+        const uint8_t on = weight.has_value();
+        check(snn_graph_edit(h_, &pre, &post, &w, &on, 1));
+    }
+    std::pair<std::vector<uint32_t>, std::vector<float>> incoming_connections(uint32_t post) { return graph_line(snn_graph_incoming, post); }
+    std::pair<std::vector<uint32_t>, std::vector<float>> outgoing_connections(uint32_t pre) { return graph_line(snn_graph_outgoing, pre); }
+
     // The same on a sparse handle (from_network_sparse), snn_connect_by_rules_csr: the records are applied in order and committed
     // once; edges outside their blocks keep their current weights, traces / dw / counters of the whole graph restart at 0.
     void connect_sparse(const std::vector<snn_connect_record> &records)
@@ -662,6 +681,16 @@ public:
     }
 
   private:
+    // count first, then the lists (the two-call idiom of snn_graph_incoming / snn_graph_outgoing)
+    template <class F>
+    std::pair<std::vector<uint32_t>, std::vector<float>> graph_line(F query, uint32_t which)
+    {
+        uint64_t n = 0;
+        check(query(h_, which, nullptr, nullptr, 0, &n));
+        std::pair<std::vector<uint32_t>, std::vector<float>> out{std::vector<uint32_t>(n), std::vector<float>(n)};
+        if (n) check(query(h_, which, out.first.data(), out.second.data(), n, &n));
+        return out;
+    }
     template <class V>
     std::vector<std::vector<V>> cross_rows(size_t pre, size_t post, bool counter)
     {

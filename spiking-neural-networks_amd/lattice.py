@@ -21,17 +21,24 @@ from .network import (CUSTOM, NT_CUSTOM, RC_CUSTOM, REFRACTORINESS_CUSTOM, ST_CU
                       RC_APPROXIMATE, RC_DESTEXHE, ST_NONE, ST_POISSON, ST_RATE, ConnectionRule, WeightRule)
 
 
-def _rule_graph(rule, weight, pre_shape, post_shape):
-    """(mask, weights) of a ConnectionRule / WeightRule pair on two grids: what snn_connect_by_rule writes on the device,
-    from the records' host twins.  None when the arguments are the reference's two closures."""
+def _rule_records(rule, weight):
+    """(ConnectionRule, WeightRule) when connect(...) was handed records; None when the arguments are the reference's two closures"""
     if not isinstance(rule, ConnectionRule):
         if isinstance(weight, WeightRule):
             raise TypeError("a WeightRule goes with a ConnectionRule, not with a closure")
         return None
     if weight is not None and not isinstance(weight, WeightRule):
         raise TypeError("a ConnectionRule goes with a WeightRule (or None: every edge weighs 1), not with a closure")
-    weight = WeightRule.constant(1.0) if weight is None else weight
-    return rule.mask(pre_shape, post_shape), weight.values(pre_shape, post_shape)
+    return rule, (WeightRule.constant(1.0) if weight is None else weight)
+
+
+def _rule_graph(rule, weight, pre_shape, post_shape):
+    """(mask, weights) of a ConnectionRule / WeightRule pair on two grids: what snn_connect_by_rule writes on the device,
+    from the records' host twins.  None when the arguments are the reference's two closures."""
+    records = _rule_records(rule, weight)
+    if records is None:
+        return None
+    return records[0].mask(pre_shape, post_shape), records[1].values(pre_shape, post_shape)
 
 
 class IonotropicNeurotransmitterType(enum.IntEnum):      # iterate_and_spike/mod.rs:1068-1073
@@ -444,8 +451,13 @@ class Lattice:
     def __init__(self, id=0):
         self.id = id
         self.cell_grid = []
-        self.weights = np.zeros((0, 0), np.float32)            # AdjacencyMatrix, index = row*cols + col
-        self.connections = np.zeros((0, 0), np.uint32)
+        # AdjacencyMatrix, index = row*cols + col.  The two matrices exist only once somebody asks for them (`weights` /
+        # `connections` below): until then the graph is RULE-HELD -- the last ConnectionRule / WeightRule pair connect() was
+        # handed (None: no edge at all), and, while a network on the device runs this lattice, that handle's matrix.
+        self._weights = np.zeros((0, 0), np.float32)
+        self._connections = np.zeros((0, 0), np.uint32)
+        self._rule = None
+        self._device = None                                    # the LatticeNetworkGPU whose handle holds this lattice's weights
         self.update_grid_history = False
         self.update_graph_history = False
         self.electrical_synapse = True
@@ -479,22 +491,80 @@ class Lattice:
     def get_every_node(self):
         return set(self.position_to_index)
 
+    # -- the graph: rule-held until a full matrix is asked for ------------------------------------
+    @property
+    def rule_held(self):
+        """no host matrices: the graph is the last record of connect() (or empty), or lives on the device"""
+        return self._weights is None
+
+    def _live(self):
+        """the network on the device that runs this lattice, while its handle exists"""
+        g = self._device
+        return g if g is not None and g._dn is not None else None
+
+    def _materialise(self):
+        """the two N x N matrices, from the device while a handle holds the weights, else from the record's host twins; from then
+        on the lattice behaves as it always has"""
+        if self._weights is not None:
+            return
+        shape, n = (self.rows, self.cols), self.rows * self.cols
+        g = self._live()
+        if g is not None:
+            w, c = g._block(self.id)
+        elif self._rule is None:
+            w, c = np.zeros((n, n), np.float32), np.zeros((n, n), np.uint32)
+        else:
+            on = self._rule[0].mask(shape, shape)
+            w = np.where(on, self._rule[1].values(shape, shape), np.float32(0)).astype(np.float32)
+            c = on.astype(np.uint32)
+        self._weights, self._connections, self._rule = w, c, None
+
+    @property
+    def weights(self):
+        self._materialise()
+        return self._weights
+
+    @weights.setter
+    def weights(self, value):
+        self._materialise()
+        self._weights = value
+
+    @property
+    def connections(self):
+        self._materialise()
+        return self._connections
+
+    @connections.setter
+    def connections(self, value):
+        self._materialise()
+        self._connections = value
+
+    def __deepcopy__(self, memo):
+        """a copy never carries the device reference: weights that live only there are brought home first"""
+        g = self._live()
+        if g is not None and self._weights is None and g._may_differ(self):
+            self._materialise()
+        new = type(self).__new__(type(self))
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            new.__dict__[k] = None if k == "_device" else copy.deepcopy(v, memo)
+        return new
+
     # -- building ---------------------------------------------------------------------------------
     def populate(self, neuron, num_rows, num_cols):             # neuron/mod.rs:1105-1126
         self.cell_grid = [[copy.deepcopy(neuron) for _ in range(num_cols)] for _ in range(num_rows)]
-        n = num_rows * num_cols
-        self.weights = np.zeros((n, n), np.float32)
-        self.connections = np.zeros((n, n), np.uint32)
+        self._weights = self._connections = self._rule = None      # no edge; no matrix until one is asked for
 
     def connect(self, connection_conditional, weight_logic=None):   # neuron/mod.rs:1134-1157
         """two closures on positions as in the reference, or a ConnectionRule and a WeightRule (the graph the device call
-        DeviceNetwork.connect_by_rule produces, without a Python call per pair)"""
-        graph = _rule_graph(connection_conditional, weight_logic, (self.rows, self.cols), (self.rows, self.cols))
-        if graph is not None:
-            on, w = graph
-            self.connections[...] = on
-            self.weights[...] = np.where(on, w, np.float32(0))
+        DeviceNetwork.connect_by_rule produces, without a Python call per pair).  Records replace the whole graph, so the last
+        one IS the graph: nothing of size N^2 is built until `weights` / `connections` are read"""
+        records = _rule_records(connection_conditional, weight_logic)
+        if records is not None:
+            self._weights = self._connections = None
+            self._rule = records
             return
+        self._materialise()
         pos = [(r, c) for r in range(self.rows) for c in range(self.cols)]
         for i, a in enumerate(pos):
             for j, b in enumerate(pos):
@@ -527,14 +597,49 @@ class Lattice:
         """lookup_weight(...).unwrap_or(0.) as the reference's Python class hands it out (interface
         lattices/mod.rs:114-121): an absent edge reads 0, a position outside the lattice is a KeyError"""
         i, j = self._index(presynaptic), self._index(postsynaptic)
+        if self._weights is None:
+            on, w = self._rule_held_pairs([i], [j])
+            return float(w[0, 0]) if on[0, 0] else 0.0
         return float(self.weights[i, j]) if self.connections[i, j] else 0.0
+
+    def _rule_held_pairs(self, pre_index, post_index):
+        """(connected bool, weights float32) [n_pre, n_post] of the lattice-local pairs pre_index x post_index (None: every cell)
+        of a rule-held lattice -- from the device while a handle holds the weights (right under plasticity), else from the record's
+        twins on those rows / columns.  O(pairs asked for)."""
+        shape, n = (self.rows, self.cols), self.rows * self.cols
+        g = self._live()
+        if g is not None:
+            first = g._dn.lattice_range(self.id)[0]
+            if pre_index is None:                                  # one column
+                on, w = np.zeros((n, 1), bool), np.zeros((n, 1), np.float32)
+                index, weights = g._dn.graph_incoming(first + post_index[0])
+                mine = (index >= first) & (index < first + n)
+                on[index[mine] - first, 0], w[index[mine] - first, 0] = True, weights[mine]
+                return on, w
+            if post_index is None:                                 # one row
+                on, w = np.zeros((1, n), bool), np.zeros((1, n), np.float32)
+                index, weights = g._dn.graph_outgoing(first + pre_index[0])
+                mine = (index >= first) & (index < first + n)
+                on[0, index[mine] - first], w[0, index[mine] - first] = True, weights[mine]
+                return on, w
+            pre, post = np.meshgrid(np.asarray(pre_index) + first, np.asarray(post_index) + first, indexing="ij")
+            w, on = g._dn.graph_lookup(pre.reshape(-1), post.reshape(-1))
+            return on.reshape(pre.shape), w.reshape(pre.shape)
+        if self._rule is None:
+            size = (n if pre_index is None else len(pre_index), n if post_index is None else len(post_index))
+            return np.zeros(size, bool), np.zeros(size, np.float32)
+        return (self._rule[0].mask(shape, shape, pre_index, post_index), self._rule[1].values(shape, shape, pre_index, post_index))
 
     def get_incoming_connections(self, position):
         j = self._index(position)
+        if self._weights is None:
+            return {(i // self.cols, i % self.cols) for i in np.nonzero(self._rule_held_pairs(None, [j])[0][:, 0])[0]}
         return {(i // self.cols, i % self.cols) for i in np.nonzero(self.connections[:, j])[0]}
 
     def get_outgoing_connections(self, position):
         i = self._index(position)
+        if self._weights is None:
+            return {(j // self.cols, j % self.cols) for j in np.nonzero(self._rule_held_pairs([i], None)[0][0])[0]}
         return {(j // self.cols, j % self.cols) for j in np.nonzero(self.connections[i])[0]}
 
     def set_dt(self, dt):                                       # neuron/mod.rs:649-652
@@ -786,8 +891,7 @@ class LatticeNetwork:
         """lookup inside a lattice (same id) or in the connecting graph; an absent edge reads 0 (:914-940)"""
         if presynaptic.id == postsynaptic.id:
             l = self._lattice(presynaptic.id)
-            i, j = l._index(presynaptic.pos), l._index(postsynaptic.pos)
-            return float(l.weights[i, j]) if l.connections[i, j] else 0.0
+            return Lattice.get_weight(l, presynaptic.pos, postsynaptic.pos)
         nodes = self._node_set()
         if presynaptic not in nodes or postsynaptic not in nodes:
             raise KeyError("GraphError::PositionNotFound")
@@ -1133,6 +1237,7 @@ class LatticeNetworkGPU:
         self._device = device
         self._dn = None
         self._graph_hist = {}
+        self._plastic = set()           # ids of the lattices that ran with do_plasticity since the upload
         # when a lattice's weight snapshot is taken: 2 = before the step's weight updates (LatticeNetwork::iterate,
         # neuron/mod.rs:2450-2461), 1 = after them (a lone Lattice, neuron/mod.rs:904-910 -- what LatticeGPU passes)
         self._graph_hist_order = graph_history_order
@@ -1205,9 +1310,31 @@ class LatticeNetworkGPU:
 
     def _dirty(self):
         if self._dn is not None:
+            # the device copy goes: a rule-held lattice whose weights may no longer be its rule's brings them home first (a static
+            # one stays rule-held -- the rule recreates its weights bit for bit)
+            for l in self.network.lattices.values():
+                if getattr(l, "_device", None) is self:
+                    if l.rule_held and self._may_differ(l):
+                        l._materialise()
+                    l._device = None
             self._dn.close()
             self._dn = None
             self._graph_hist = {}
+            self._plastic = set()
+
+    def _may_differ(self, lattice):
+        """whether the handle's weights of a rule-held lattice may differ from what its rule gives: plasticity (STDP, BCM) was on
+        for it in a run since the upload"""
+        return lattice.id in self._plastic
+
+    def _block(self, id):
+        """(weights float32[n, n], connections uint32[n, n]) of lattice `id` as the handle holds them now"""
+        first, count = self._dn.lattice_range(id)
+        w, c = self._dn.get_graph_rows(first, count)
+        return w[:, first:first + count].copy(), c[:, first:first + count].copy()
+
+    def _note_plasticity(self):
+        self._plastic |= {id for id, l in self.network.lattices.items() if l.do_plasticity}
 
     def _ensure(self):
         if self._dn is not None:
@@ -1252,16 +1379,27 @@ class LatticeNetworkGPU:
         nn, nt = dn.n_neurons, dn.n_tot
         if nn == 0 or nt == 0:
             return
-        w = np.zeros((nt, nn), np.float32)
-        c = np.zeros((nt, nn), np.uint32)
+        # A freshly finalized dense handle holds no edge.  A materialised lattice uploads its own rows (its block, every other
+        # column absent); a rule-held one is one connect_by_rule on the device and a lattice that was never connected leaves its
+        # block empty; the connecting graph's edges go up last, in one edit.  Nothing of size N^2 exists on the host unless a
+        # lattice already holds its matrices.
         for id, l in net.lattices.items():
+            l._device = self
             first, count = dn.lattice_range(id)
-            w[first:first + count, first:first + count] = l.weights
-            c[first:first + count, first:first + count] = l.connections
-        for (pre, post), weight in net.connecting.items():
-            i, j = self._global(pre), self._global(post)
-            w[i, j], c[i, j] = weight, 1
-        dn.set_graph_rows(0, w, c)
+            if not l.rule_held and count:
+                w = np.zeros((count, nn), np.float32)
+                c = np.zeros((count, nn), np.uint32)
+                w[:, first:first + count] = l.weights
+                c[:, first:first + count] = l.connections
+                dn.set_graph_rows(first, w, c)
+                del w, c
+        for id, l in net.lattices.items():
+            if l.rule_held and l._rule is not None:
+                dn.connect_by_rule(id, id, *l._rule)
+        if net.connecting:
+            keys = list(net.connecting)
+            dn.graph_edit([self._global(a) for a, _ in keys], [self._global(b) for _, b in keys],
+                          np.array([net.connecting[k] for k in keys], np.float32))
         for id, l in net.lattices.items():
             if isinstance(l, RewardModulatedLattice):
                 m = l.reward_modulator
@@ -1299,6 +1437,7 @@ class LatticeNetworkGPU:
         dn, net = self._ensure(), self.network
         dn.set_synapses(net.electrical_synapse, net.chemical_synapse)
         self._history_flags()
+        self._note_plasticity()
         dn.run(iterations)
         self._download()
 
@@ -1309,6 +1448,7 @@ class LatticeNetworkGPU:
         dn, net = self._ensure(), self.network
         dn.set_synapses(net.electrical_synapse, net.chemical_synapse)
         self._history_flags()
+        self._note_plasticity()
         dn.run_with_reward(float(reward))
         if download:
             self._download()
@@ -1317,16 +1457,13 @@ class LatticeNetworkGPU:
         dn, net = self._dn, self.network
         net.internal_clock = dn.clock
         nn, nt = dn.n_neurons, dn.n_tot
-        w = c = None
-        if nn and nt:
-            w, c = dn.get_graph_rows(0, nt)
+        have_graph = bool(nn and nt)
         for id, l in net.lattices.items():
             _download_neurons(dn, id, _flat(l))
             l.internal_clock = net.internal_clock
-            if w is not None:
+            if have_graph and not l.rule_held:                  # (a rule-held lattice's weights stay on the device: asked there)
                 first, count = dn.lattice_range(id)
-                l.weights = w[first:first + count, first:first + count].copy()
-                l.connections = c[first:first + count, first:first + count].copy()
+                l.weights, l.connections = self._block(id)
                 if isinstance(l, RewardModulatedLattice):
                     l.traces = dn.get_trace_rows(first, count)[:, first:first + count].copy()
                     l.reward_modulator.dopamine = float(dn.dopamine(id))
@@ -1348,9 +1485,11 @@ class LatticeNetworkGPU:
                     for cell, clk, cnt in zip(cells, dn.get_attr(id, "internal_clock"),
                                               dn.get_attr(id, "counter", dtype=np.uint32)):
                         cell.internal_clock, cell.counter = float(clk), int(cnt)
-        if w is not None:
-            for key in net.connecting:
-                net.connecting[key] = float(w[self._global(key[0]), self._global(key[1])])
+        if have_graph and net.connecting:
+            keys = list(net.connecting)
+            w, _ = dn.graph_lookup([self._global(a) for a, _ in keys], [self._global(b) for _, b in keys])
+            for key, weight in zip(keys, w):
+                net.connecting[key] = float(weight)
         # the histories the reference keeps in its lattices (GridVoltageHistory; AdjacencyMatrix::history)
         for id, l in list(net.lattices.items()) + list(net.spike_train_lattices.items()):
             if l.update_grid_history and l.rows * l.cols:
@@ -1515,6 +1654,7 @@ class RewardModulatedLatticeGPU(LatticeGPU):
     def update(self):
         net = self._ensure()
         net._dn.set_synapses(self._lattice.electrical_synapse, self._lattice.chemical_synapse)
+        net._note_plasticity()
         net._dn.run(1)
 
     def sync(self):

@@ -46,11 +46,21 @@ RULE_ALL, RULE_CHEBYSHEV, RULE_EUCLIDEAN, RULE_SAME_POSITION = 0, 1, 2, 3      #
 WEIGHT_CONSTANT, WEIGHT_UNIFORM = 0, 1                                         # snn_weight_rule
 
 
-def _pair_grid(pre_shape, post_shape):
+def _pair_grid(pre_shape, post_shape, pre_index=None, post_index=None):
     """positions and pair index of every (pre, post) pair of two grids (rows, cols): pre row / col as columns [n_pre, 1], post
-    row / col as rows [1, n_post], idx = i_pre * n_post + i_post as uint64 [n_pre, n_post]"""
+    row / col as rows [1, n_post], idx = i_pre * n_post + i_post as uint64 [n_pre, n_post].  pre_index / post_index (arrays of
+    lattice-local indices): only those rows / columns of the grid of pairs, in the order given -- the same positions and the
+    same idx, so a row, a column or a single pair costs O(N)"""
     (pr, pc), (qr, qc) = pre_shape, post_shape
-    i, j = np.arange(pr * pc, dtype=np.int64)[:, None], np.arange(qr * qc, dtype=np.int64)[None, :]
+
+    def pick(index, n, name):
+        if index is None:
+            return np.arange(n, dtype=np.int64)
+        index = np.asarray(index, dtype=np.int64).reshape(-1)
+        if index.size and (index.min() < 0 or index.max() >= n):
+            raise IndexError(f"{name} outside the lattice's {n} cells")
+        return index
+    i, j = pick(pre_index, pr * pc, "pre_index")[:, None], pick(post_index, qr * qc, "post_index")[None, :]
     idx = i.astype(np.uint64) * np.uint64(qr * qc) + j.astype(np.uint64)
     return i // max(pc, 1), i % max(pc, 1), j // max(qc, 1), j % max(qc, 1), idx
 
@@ -98,9 +108,10 @@ class ConnectionRule:
         return (f"ConnectionRule(kind={self.kind}, extent={self.extent}, self_edges={self.self_edges}, "
                 f"probability={self.probability}, seed={self.seed})")
 
-    def mask(self, pre_shape, post_shape):
-        """bool[n_pre, n_post]: the pairs the device call connects, for grids (rows, cols)"""
-        ra, ca, rb, cb, idx = _pair_grid(pre_shape, post_shape)
+    def mask(self, pre_shape, post_shape, pre_index=None, post_index=None):
+        """bool[n_pre, n_post]: the pairs the device call connects, for grids (rows, cols); with pre_index / post_index (lattice-local
+        indices) those rows / columns of it only"""
+        ra, ca, rb, cb, idx = _pair_grid(pre_shape, post_shape, pre_index, post_index)
         dr, dc = np.abs(ra - rb), np.abs(ca - cb)
         on = np.ones(idx.shape, bool)
         if self.kind == RULE_CHEBYSHEV:
@@ -147,9 +158,10 @@ class WeightRule:
     def __repr__(self):
         return f"WeightRule(kind={self.kind}, lo={self.lo}, hi={self.hi}, seed={self.seed})"
 
-    def values(self, pre_shape, post_shape):
-        """float32[n_pre, n_post]: the weight the device call gives each pair (whether or not the rule connects it)"""
-        idx = _pair_grid(pre_shape, post_shape)[4]
+    def values(self, pre_shape, post_shape, pre_index=None, post_index=None):
+        """float32[n_pre, n_post]: the weight the device call gives each pair (whether or not the rule connects it); with
+        pre_index / post_index (lattice-local indices) those rows / columns of it only"""
+        idx = _pair_grid(pre_shape, post_shape, pre_index, post_index)[4]
         lo, hi = np.float32(self.lo), np.float32(self.hi)
         if self.kind == WEIGHT_CONSTANT:
             return np.full(idx.shape, lo, np.float32)
@@ -283,6 +295,57 @@ class DeviceNetwork:
         self._check(self._L.snn_get_graph_rows(self._h, pre_begin, pre_count, w.ctypes.data_as(_lib.f32p),
                                               c.ctypes.data_as(_lib.u32p)))
         return w, c
+
+    # the Graph trait on the device matrix (graph/mod.rs:42-72); interleaved global indices, dense handles
+    @staticmethod
+    def _pairs(pre, post):
+        p = np.ascontiguousarray(np.asarray(pre).reshape(-1), dtype=np.uint32)
+        q = np.ascontiguousarray(np.asarray(post).reshape(-1), dtype=np.uint32)
+        if p.size != q.size:
+            raise ValueError("pre and post must have equal lengths")
+        if np.any(p != np.asarray(pre).reshape(-1)) or np.any(q != np.asarray(post).reshape(-1)):
+            raise ValueError("indices must be non-negative integers below 2^32")
+        return p, q
+
+    def graph_lookup(self, pre, post):
+        """lookup_weight for the pairs (pre[k], post[k]): (weights float32[n], connected bool[n]); an absent edge reads 0.0 / False"""
+        p, q = self._pairs(pre, post)
+        w, c = _out(p.size, np.float32), _out(p.size, np.uint8)
+        self._check(self._L.snn_graph_lookup(self._h, p.ctypes.data_as(_lib.u32p), q.ctypes.data_as(_lib.u32p), p.size,
+                                            w.ctypes.data_as(_lib.f32p), c.ctypes.data_as(_lib.u8p)))
+        return w, c != 0
+
+    def graph_edit(self, pre, post, weights, connected=None):
+        """edit_weight for the pairs (pre[k], post[k]): Some(weights[k]) where connected[k] (None: everywhere), None elsewhere.  Applied
+        as if one after another: of a pair listed twice the last wins.  A NaN weight of a connected pair is refused."""
+        p, q = self._pairs(pre, post)
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+        if np.ndim(weights) == 0:                # one weight for every pair
+            w = np.full(p.size, w[0], np.float32)
+        c = np.ones(p.size, np.uint8) if connected is None else np.ascontiguousarray(np.asarray(connected).reshape(-1) != 0, dtype=np.uint8)
+        if w.size != p.size or c.size != p.size:
+            raise ValueError("weights / connected must have one entry per pair")
+        self._check(self._L.snn_graph_edit(self._h, p.ctypes.data_as(_lib.u32p), q.ctypes.data_as(_lib.u32p),
+                                          w.ctypes.data_as(_lib.f32p), c.ctypes.data_as(_lib.u8p), p.size))
+
+    def _graph_line(self, fn, which):
+        n = C.c_uint64()
+        self._check(fn(self._h, which, None, None, 0, C.byref(n)))
+        index, w = _out(int(n.value), np.uint32), _out(int(n.value), np.float32)
+        if n.value:
+            self._check(fn(self._h, which, index.ctypes.data_as(_lib.u32p), w.ctypes.data_as(_lib.f32p), index.size, C.byref(n)))
+            if n.value != index.size:
+                raise RuntimeError("the graph changed between the two calls of a line query")
+        return index, w
+
+    def graph_incoming(self, post):
+        """get_incoming_connections: (pre index uint32[count] ascending, weights float32[count]) of the edges into `post`"""
+        return self._graph_line(self._L.snn_graph_incoming, int(post))
+
+    def graph_outgoing(self, pre):
+        """get_outgoing_connections: (post index uint32[count] ascending, weights float32[count]) of the edges out of `pre` (a shard
+        handle: into the columns it owns)"""
+        return self._graph_line(self._L.snn_graph_outgoing, int(pre))
 
     def set_graph_csr(self, row_ptr, pre_index, weights):
         """CSR by OWNED postsynaptic neuron in ascending global order (self.owned): row_ptr[n_owned + 1], pre_index
