@@ -196,7 +196,8 @@ int snn_fill_graph_synthetic(snn_network_t *net, uint64_t seed, float lo, float 
  * weight_rule, a non-finite w_lo / w_hi or, with SNN_WEIGHT_UNIFORM, a w_hi - w_lo that overflows -- NaN is the absent-edge
  * sentinel -- (SNN_ERR_BAD_ARG). */
 typedef enum { SNN_RULE_ALL = 0, SNN_RULE_CHEBYSHEV = 1, SNN_RULE_EUCLIDEAN = 2, SNN_RULE_SAME_POSITION = 3 } snn_connection_rule;
-typedef enum { SNN_WEIGHT_CONSTANT = 0, SNN_WEIGHT_UNIFORM = 1 } snn_weight_rule;
+/* (SNN_WEIGHT_DISPLACEMENT: snn_connect_by_spec / snn_connect_by_specs_csr only, below) */
+typedef enum { SNN_WEIGHT_CONSTANT = 0, SNN_WEIGHT_UNIFORM = 1, SNN_WEIGHT_DISPLACEMENT = 2 } snn_weight_rule;
 int snn_connect_by_rule(snn_network_t *net, uint32_t pre_id, uint32_t post_id, uint32_t rule, uint32_t extent,
                         int self_edges, float probability, uint64_t edge_seed, uint32_t weight_rule, float w_lo,
                         float w_hi, uint64_t weight_seed);
@@ -268,6 +269,41 @@ typedef struct snn_connect_record {
     uint32_t weight_rule; float w_lo, w_hi; uint64_t weight_seed;
 } snn_connect_record;
 int snn_connect_by_rules_csr(snn_network_t *net, const snn_connect_record *records, uint32_t n_records);
+
+/* Connect by rule on a torus, weights from a displacement table: the two calls above with an extension -- the ring and torus
+ * attractors of the reference's experiments (connect(lambda x, y: True, w) with w a function of the wrapped displacement between
+ * the two positions: interface_gpu/experiments/hd_model.py, grid_cell_electrical_model.py).  `record` has every field with the
+ * meaning it has above; with wrap == 0 and weight_rule < 2 the two calls write, bit for bit, what the two calls above write.
+ * For a pre position a = (ra, ca) and a post position b = (rb, cb):
+ *   periods    P_r = max(pre rows, post rows), P_c = max(pre cols, post cols)
+ *   distances  dr0 = |ra - rb|; dr = (wrap & SNN_WRAP_ROWS) ? min(dr0, P_r - dr0) : dr0; dc likewise with SNN_WRAP_COLS and P_c.
+ *              SNN_RULE_CHEBYSHEV and SNN_RULE_EUCLIDEAN use dr, dc as above (integer arithmetic, the squared radius);
+ *              SNN_RULE_ALL, SNN_RULE_SAME_POSITION, self_edges, the draw, the pair index and the constant and uniform weights
+ *              do not depend on wrap.
+ *   SNN_WEIGHT_DISPLACEMENT   the weight is table[u * table_cols + v] with
+ *              u = (wrap & SNN_WRAP_ROWS) ? (rb - ra) mod P_r : rb - ra + (pre rows - 1), v likewise with columns;
+ *              table_rows must be P_r where rows wrap and pre rows + post rows - 1 where they do not, table_cols likewise.
+ *              A NaN entry is None for that pair whatever the rule says; w_lo, w_hi and weight_seed are not read.  The table is
+ *              read during the call only (it is copied into a device buffer that is freed before the call returns): O(N) words
+ *              where the graph has O(N^2), filled by the host with whatever function of the displacement the user has.
+ * With another weight_rule, table, table_rows and table_cols are not read.
+ * On sparse handles a SNN_WEIGHT_DISPLACEMENT record takes its candidates from its rule: SNN_RULE_ALL visits every presynaptic
+ * cell of every row (on a large handle give the table a radius rule), a distance rule its window -- on a ring at most two runs of
+ * rows by at most two runs of columns, visited in ascending presynaptic index.
+ * Refused as the calls above refuse, and with SNN_ERR_BAD_ARG naming the argument: wrap > 3; with SNN_WEIGHT_DISPLACEMENT a null
+ * table, table_rows or table_cols other than the above, an infinite entry ("table"; found by a scan before anything changes).  A
+ * refused call leaves the graph as it was -- as do the calls above, a call that fails while it allocates the table's device
+ * buffer has first applied a deferred plasticity update to the old weights, which the next step would have applied anyway; snn_connect_by_specs_csr names "record k: ".  Shard handles, by-lattice shards and
+ * reward-modulated handles: as with the calls above. */
+enum { SNN_WRAP_ROWS = 1, SNN_WRAP_COLS = 2 };
+typedef struct snn_connect_spec {
+    snn_connect_record record;
+    uint32_t wrap;                      /* SNN_WRAP_ROWS | SNN_WRAP_COLS */
+    uint32_t table_rows, table_cols;    /* SNN_WEIGHT_DISPLACEMENT only */
+    const float *table;                 /* host, row-major [table_rows][table_cols] */
+} snn_connect_spec;
+int snn_connect_by_spec(snn_network_t *net, const snn_connect_spec *spec);                           /* dense handles */
+int snn_connect_by_specs_csr(snn_network_t *net, const snn_connect_spec *specs, uint32_t n_specs);   /* sparse handles */
 
 /* ---- switches (Lattice / LatticeNetwork pub fields, neuron/mod.rs:570-586, 1577-1588) -- */
 

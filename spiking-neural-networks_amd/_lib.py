@@ -142,6 +142,12 @@ class ConnectRecord(C.Structure):
                 ("weight_rule", C.c_uint32), ("w_lo", C.c_float), ("w_hi", C.c_float), ("weight_seed", C.c_uint64)]
 
 
+class ConnectSpec(C.Structure):
+    """snn_connect_spec of include/snn_amd.h (snn_connect_by_spec, snn_connect_by_specs_csr)"""
+    _fields_ = [("record", ConnectRecord), ("wrap", C.c_uint32), ("table_rows", C.c_uint32), ("table_cols", C.c_uint32),
+                ("table", C.POINTER(C.c_float))]
+
+
 EXCHANGE_ALLGATHER, EXCHANGE_HALO = 0, 1
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)      # snn_exchange_fn(user, hip_stream)
@@ -198,6 +204,7 @@ SIGNATURES = {
     "snn_fill_graph_synthetic": (C.c_int, [H, C.c_uint64, C.c_float, C.c_float, C.c_int]),
     "snn_connect_by_rule": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_uint64,
                                       C.c_uint32, C.c_float, C.c_float, C.c_uint64]),
+    "snn_connect_by_spec": (C.c_int, [H, C.POINTER(ConnectSpec)]),
     "snn_graph_lookup": (C.c_int, [H, u32p, u32p, C.c_size_t, f32p, u8p]),
     "snn_graph_edit": (C.c_int, [H, u32p, u32p, f32p, u8p, C.c_size_t]),
     "snn_graph_incoming": (C.c_int, [H, C.c_uint32, u32p, f32p, C.c_uint64, u64p]),
@@ -208,6 +215,7 @@ SIGNATURES = {
     "snn_graph_csr_nnz": (C.c_int, [H, u64p]),
     "snn_get_graph_csr_structure": (C.c_int, [H, u64p, u32p, C.c_uint64]),
     "snn_connect_by_rules_csr": (C.c_int, [H, C.POINTER(ConnectRecord), C.c_uint32]),
+    "snn_connect_by_specs_csr": (C.c_int, [H, C.POINTER(ConnectSpec), C.c_uint32]),
     "snn_set_synapses": (C.c_int, [H, C.c_int, C.c_int]),
     "snn_set_plasticity": (C.c_int, [H, C.c_uint32] + [C.c_float] * 5 + [C.c_int]),
     "snn_set_history": (C.c_int, [H, C.c_int, C.c_int]),

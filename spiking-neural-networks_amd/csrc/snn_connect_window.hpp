@@ -45,4 +45,35 @@ SNN_WINDOW_FN ConnectSpan connect_window_span(uint32_t center, uint32_t e, uint3
     return s;
 }
 
+// The same window on a ring of `period` cells (snn_connect_by_spec with a wrap flag; period >= size, center < period): the cells
+// x of 0 .. size-1 with min(|x - center|, period - |x - center|) <= e.  They are the union of [0, center+e-period],
+// [max(0, center-e), min(size-1, center+e)] and [center-e+period, size-1].  With 2e + 1 >= period that is every cell; otherwise
+// the first piece needs center + e >= period and the last center < e, which together give 2e > period: at most two pieces hold a
+// cell, and as 2e + 1 < period no two of them touch.  Returned as two ascending runs, a below b, either of which may be empty.
+// period == 0: no wrap-around -- a = connect_window_span, b empty.
+struct ConnectSpans { ConnectSpan a, b; };
+
+SNN_WINDOW_FN ConnectSpans connect_window_spans(uint32_t center, uint32_t e, uint32_t size, uint32_t period)
+{
+    ConnectSpans s{connect_window_span(center, e, size), ConnectSpan{size, 0u}};
+    if (period == 0u || size == 0u) return s;
+    if (2ull * e + 1ull >= (uint64_t)period) { s.a = ConnectSpan{0u, size}; return s; }
+    const uint64_t reach = (uint64_t)center + e;
+    if (reach >= (uint64_t)period) {                 // the window runs over the end of the ring: cells 0 .. reach - period, below the middle piece
+        const uint64_t last = reach - period;
+        s.b = s.a;
+        s.a = ConnectSpan{0u, last < (uint64_t)size - 1u ? (uint32_t)last + 1u : size};
+    } else if (center < e) {                         // ... or below cell 0: cells center - e + period .., above the middle piece
+        const uint64_t first = (uint64_t)center + period - e;
+        if (first < (uint64_t)size) s.b = ConnectSpan{(uint32_t)first, size - (uint32_t)first};
+    }
+    return s;
+}
+
+// the cell with ordinal `k` (0 <= k < a.count + b.count) of the two runs taken in ascending order
+SNN_WINDOW_FN uint32_t connect_spans_cell(const ConnectSpans &s, uint32_t k)
+{
+    return k < s.a.count ? s.a.first + k : s.b.first + (k - s.a.count);
+}
+
 } // namespace snn

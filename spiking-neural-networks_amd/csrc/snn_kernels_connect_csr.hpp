@@ -104,6 +104,100 @@ __global__ __launch_bounds__(256) void k_connect_csr(const ConnectCsrArgs a)
     }
 }
 
+// snn_connect_by_specs_csr: the merge of k_connect_csr, statement for statement, for the records it does not cover
+// (connect_spec_is_plain): the table with every rule, WRAP with the two distance rules.  A kernel of its own so that the
+// instantiations of k_connect_csr stay what they are.  WRAP: the window of a wrapped dimension is at most two ascending runs of
+// cells (connect_window_spans), so candidate t is still (row ordinal, column ordinal) over sorted rows x sorted columns, ascending
+// in the pre index.  A displacement record takes its candidates from its rule -- every presynaptic cell under CONNECT_ALL, the
+// window under a radius -- and a NaN entry of the table drops the pair.  Grid and block as k_connect_csr.
+struct ConnectCsrSpecArgs { ConnectCsrArgs c; ConnectSpecExt x; };
+template <int RULE, int WEIGHT, bool THIN, bool SELF, bool WRAP, bool FILL>
+__global__ __launch_bounds__(256) void k_connect_csr_spec(const ConnectCsrSpecArgs s)
+{
+    const ConnectCsrArgs &a = s.c;
+    const ConnectSpecExt &x = s.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const uint32_t waves = gridDim.x * 4u;
+    const uint32_t pre_end = a.c.pre_first + a.c.pre_count;
+    for (uint32_t row = blockIdx.x * 4u + (threadIdx.x >> 6); row < a.n_rows; row += waves) {
+        const uint32_t o0 = a.old_ptr[row], o1 = a.old_ptr[row + 1];
+        uint32_t out = FILL ? a.new_ptr[row] : 0u;                 // wave-uniform from here on
+        if (row < a.c.col0 || row >= a.c.col0 + a.c.n_cols) {
+            if (FILL)
+                for (uint32_t k = o0 + lane; k < o1; k += 64u) { a.new_pre[out + (k - o0)] = a.old_pre[k]; a.new_w[out + (k - o0)] = a.old_w[k]; }
+            else if (lane == 0) a.new_len[row] = o1 - o0;
+            continue;
+        }
+        // the old row: [o0, o0 + n_low) lies below the block, [o0 + n_mid, o1) above it
+        uint32_t n_low = 0, n_mid = 0;
+        for (uint32_t k0 = o0; k0 < o1; k0 += 64u) {
+            const uint32_t k = k0 + lane;
+            const bool have = k < o1;
+            const uint32_t p = have ? a.old_pre[k] : 0xFFFFFFFFu;
+            const bool low = have && p < a.c.pre_first;
+            n_low += (uint32_t)__popcll(__ballot(low));
+            n_mid += (uint32_t)__popcll(__ballot(have && p < pre_end));
+            if (FILL && low) { a.new_pre[out + (k - o0)] = p; a.new_w[out + (k - o0)] = a.old_w[k]; }
+        }
+        out += n_low;
+        // the rule's entries
+        const uint32_t j = a.c.post_i0 + (row - a.c.col0);
+        const uint32_t rb = j / a.c.post_cols, cb = j - rb * a.c.post_cols;
+        const uint32_t i_same = (cb < a.c.pre_cols && rb < a.c.pre_rows) ? rb * a.c.pre_cols + cb : 0xFFFFFFFFu;
+        uint32_t n_cand, r0 = 0, c0 = 0, width = 1;
+        ConnectSpans rs2{}, cs2{};
+        if ((RULE == CONNECT_CHEBYSHEV || RULE == CONNECT_EUCLIDEAN) && WRAP) {
+            rs2 = connect_window_spans(rb, a.window, a.c.pre_rows, x.period_r);
+            cs2 = connect_window_spans(cb, a.window, a.c.pre_cols, x.period_c);
+            width = cs2.a.count + cs2.b.count;
+            n_cand = (rs2.a.count + rs2.b.count) * width;
+        } else if (RULE == CONNECT_CHEBYSHEV || RULE == CONNECT_EUCLIDEAN) {
+            const ConnectSpan rs = connect_window_span(rb, a.window, a.c.pre_rows), cs = connect_window_span(cb, a.window, a.c.pre_cols);
+            r0 = rs.first; c0 = cs.first; width = cs.count;
+            n_cand = rs.count * cs.count;
+        } else if (RULE == CONNECT_SAME_POSITION) {
+            n_cand = i_same != 0xFFFFFFFFu ? 1u : 0u;
+        } else {
+            n_cand = a.c.pre_count;
+        }
+        for (uint32_t t0 = 0; t0 < n_cand; t0 += 64u) {
+            const uint32_t t = t0 + lane;
+            uint32_t i = t, ra = 0, ca = 0;
+            if (RULE == CONNECT_CHEBYSHEV || RULE == CONNECT_EUCLIDEAN) {
+                const uint32_t wr = t / width;
+                if (WRAP) {
+                    if (t < n_cand) { ra = connect_spans_cell(rs2, wr); ca = connect_spans_cell(cs2, t - wr * width); }
+                } else {
+                    ra = r0 + wr; ca = c0 + (t - wr * width);
+                }
+                i = ra * a.c.pre_cols + ca;
+            }
+            if (RULE == CONNECT_SAME_POSITION) i = i_same;
+            if (WEIGHT == CONNECT_DISPLACEMENT && (RULE == CONNECT_ALL || RULE == CONNECT_SAME_POSITION) && t < n_cand) {
+                ra = i / a.c.pre_cols; ca = i - ra * a.c.pre_cols;          // (the table is indexed by position under every rule)
+            }
+            float v = quiet_nan();
+            if (t < n_cand)
+                v = connect_spec_value<RULE, WEIGHT, THIN, SELF, WRAP>(a.c, x, i, i_same, ra, ca, rb, cb, (uint64_t)i * a.c.post_count + j);
+            const bool on = v == v;                                // NaN: absent
+            const unsigned long long mask = __ballot(on);
+            if (FILL && on) {
+                const uint32_t at = out + (uint32_t)__popcll(mask & below);
+                a.new_pre[at] = a.c.pre_first + i;
+                a.new_w[at] = v;
+            }
+            out += (uint32_t)__popcll(mask);
+        }
+        // the old entries above the block
+        if (FILL) {
+            for (uint32_t k = o0 + n_mid + lane; k < o1; k += 64u) { a.new_pre[out + (k - o0 - n_mid)] = a.old_pre[k]; a.new_w[out + (k - o0 - n_mid)] = a.old_w[k]; }
+        } else if (lane == 0) {
+            a.new_len[row] = out + (o1 - o0 - n_mid);
+        }
+    }
+}
+
 // The handle's SELL-64 graph as plain CSR: entry k of row r sits at slice_ptr[r / 64] + 64 k + r % 64.  One thread per row, a
 // wavefront = the 64 columns of one slice: its loads of entry k are one contiguous 256 bytes, as the step kernels read them.
 // grid (rows / 256 rounded up), 256 threads
@@ -196,6 +290,42 @@ inline connect_csr_kernel_t connect_csr_kernel(int rule, int weight, bool thin, 
     case CONNECT_SAME_POSITION: return connect_csr_kernel_weight<CONNECT_SAME_POSITION, FILL>(weight, thin, self);
     default: return connect_csr_kernel_weight<CONNECT_ALL, FILL>(weight, thin, self);
     }
+}
+
+
+typedef void (*connect_csr_spec_kernel_t)(const ConnectCsrSpecArgs);
+
+template <int RULE, int WEIGHT, bool WRAP, bool FILL>
+inline connect_csr_spec_kernel_t connect_csr_spec_kernel_flags(bool thin, bool self)
+{
+    if (thin) return self ? k_connect_csr_spec<RULE, WEIGHT, true, true, WRAP, FILL> : k_connect_csr_spec<RULE, WEIGHT, true, false, WRAP, FILL>;
+    return self ? k_connect_csr_spec<RULE, WEIGHT, false, true, WRAP, FILL> : k_connect_csr_spec<RULE, WEIGHT, false, false, WRAP, FILL>;
+}
+template <int RULE, bool FILL>
+inline connect_csr_spec_kernel_t connect_csr_spec_kernel_table(bool wrap, bool thin, bool self)
+{
+    return wrap ? connect_csr_spec_kernel_flags<RULE, CONNECT_DISPLACEMENT, true, FILL>(thin, self)
+                : connect_csr_spec_kernel_flags<RULE, CONNECT_DISPLACEMENT, false, FILL>(thin, self);
+}
+template <int RULE, bool FILL>
+inline connect_csr_spec_kernel_t connect_csr_spec_kernel_ring(int weight, bool thin, bool self)
+{
+    return weight == CONNECT_UNIFORM ? connect_csr_spec_kernel_flags<RULE, CONNECT_UNIFORM, true, FILL>(thin, self)
+                                     : connect_csr_spec_kernel_flags<RULE, CONNECT_CONSTANT, true, FILL>(thin, self);
+}
+// the instantiation for a record that is not plain (connect_spec_is_plain)
+template <bool FILL>
+inline connect_csr_spec_kernel_t connect_csr_spec_kernel(int rule, int weight, bool wrap, bool thin, bool self)
+{
+    if (weight == CONNECT_DISPLACEMENT)
+        switch (rule) {
+        case CONNECT_CHEBYSHEV: return connect_csr_spec_kernel_table<CONNECT_CHEBYSHEV, FILL>(wrap, thin, self);
+        case CONNECT_EUCLIDEAN: return connect_csr_spec_kernel_table<CONNECT_EUCLIDEAN, FILL>(wrap, thin, self);
+        case CONNECT_SAME_POSITION: return connect_csr_spec_kernel_table<CONNECT_SAME_POSITION, FILL>(wrap, thin, self);
+        default: return connect_csr_spec_kernel_table<CONNECT_ALL, FILL>(wrap, thin, self);
+        }
+    return rule == CONNECT_CHEBYSHEV ? connect_csr_spec_kernel_ring<CONNECT_CHEBYSHEV, FILL>(weight, thin, self)
+                                     : connect_csr_spec_kernel_ring<CONNECT_EUCLIDEAN, FILL>(weight, thin, self);
 }
 
 } // namespace snn

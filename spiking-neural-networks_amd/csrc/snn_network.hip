@@ -327,8 +327,10 @@ int snn_fill_graph_synthetic(snn_network_t *net, uint64_t seed, float lo, float 
 ABI_CATCH
 
 // the arguments of one connection by rule, checked (snn_connect_by_rule; `where` = "record k: " for snn_connect_by_rules_csr)
+// weight_rules: how many weight rules the call takes (CONNECT_RULE_WEIGHTS; CONNECT_SPEC_WEIGHTS for the spec calls)
 static int connect_check(const snn_network *net, const std::string &where, uint32_t pre_id, uint32_t post_id, uint32_t rule, float probability,
-                         uint32_t weight_rule, float w_lo, float w_hi, const LatticeInfo **pre_out, const LatticeInfo **post_out)
+                         uint32_t weight_rule, float w_lo, float w_hi, const LatticeInfo **pre_out, const LatticeInfo **post_out,
+                         uint32_t weight_rules)
 {
     const LatticeInfo *pre = find_lattice(net, pre_id), *post = find_lattice(net, post_id);
     if (!pre) return fail(SNN_ERR_BAD_ARG, where + "pre_id: unknown lattice id " + std::to_string(pre_id));
@@ -336,8 +338,9 @@ static int connect_check(const snn_network *net, const std::string &where, uint3
     if (post->spike_train)   // LatticeNetworkError::PostsynapticLatticeCannotBeSpikeTrain, neuron/mod.rs:1852-1854
         return fail(SNN_ERR_BAD_ARG, where + "post_id: lattice " + std::to_string(post_id) + " is a spike-train lattice, which is never postsynaptic");
     if (rule >= CONNECT_RULES) return fail(SNN_ERR_BAD_ARG, where + "rule: unknown connection rule " + std::to_string(rule));
-    if (weight_rule >= CONNECT_WEIGHTS) return fail(SNN_ERR_BAD_ARG, where + "weight_rule: unknown weight rule " + std::to_string(weight_rule));
+    if (weight_rule >= weight_rules) return fail(SNN_ERR_BAD_ARG, where + "weight_rule: unknown weight rule " + std::to_string(weight_rule));
     if (probability != probability) return fail(SNN_ERR_BAD_ARG, where + "probability is NaN");
+    if (weight_rule == CONNECT_DISPLACEMENT) { *pre_out = pre; *post_out = post; return SNN_OK; }      // (w_lo, w_hi are not read)
     if (w_lo - w_lo != 0.0f) return fail(SNN_ERR_BAD_ARG, where + "w_lo is not finite (NaN is the absent-edge sentinel of the device matrix)");
     if (w_hi - w_hi != 0.0f) return fail(SNN_ERR_BAD_ARG, where + "w_hi is not finite (NaN is the absent-edge sentinel of the device matrix)");
     if (weight_rule == CONNECT_UNIFORM && (w_hi - w_lo) - (w_hi - w_lo) != 0.0f)      // (lo + inf * u24 is +-inf, or NaN where u24 is 0)
@@ -346,17 +349,63 @@ static int connect_check(const snn_network *net, const std::string &where, uint3
     return SNN_OK;
 }
 
-int snn_connect_by_rule(snn_network_t *net, uint32_t pre_id, uint32_t post_id, uint32_t rule, uint32_t extent,
-                        int self_edges, float probability, uint64_t edge_seed, uint32_t weight_rule, float w_lo,
-                        float w_hi, uint64_t weight_seed) ABI_TRY
+// what a spec adds to connect_check: the wrap flags, and for SNN_WEIGHT_DISPLACEMENT the table -- its dimensions follow from the
+// two grids and the flags, and every entry is finite or NaN (None).  `ext`: the kernels' form of it, the table still on the host.
+static int connect_spec_check(const snn_network *net, const std::string &where, const snn_connect_spec &s, const LatticeInfo **pre_out,
+                              const LatticeInfo **post_out, ConnectSpecExt *ext)
+{
+    const snn_connect_record &r = s.record;
+    TRY(connect_check(net, where, r.pre_id, r.post_id, r.rule, r.probability, r.weight_rule, r.w_lo, r.w_hi, pre_out, post_out, CONNECT_SPEC_WEIGHTS));
+    if (s.wrap > (SNN_WRAP_ROWS | SNN_WRAP_COLS)) return fail(SNN_ERR_BAD_ARG, where + "wrap: unknown flags " + std::to_string(s.wrap));
+    const LatticeInfo *pre = *pre_out, *post = *post_out;
+    *ext = ConnectSpecExt{};
+    ext->period_r = (s.wrap & SNN_WRAP_ROWS) ? std::max(pre->rows, post->rows) : 0u;
+    ext->period_c = (s.wrap & SNN_WRAP_COLS) ? std::max(pre->cols, post->cols) : 0u;
+    if (r.weight_rule != CONNECT_DISPLACEMENT) return SNN_OK;        // (table, table_rows and table_cols are not read)
+    ext->u_bias = pre->rows ? pre->rows - 1u : 0u;
+    ext->v_bias = pre->cols ? pre->cols - 1u : 0u;
+    const uint64_t rows = ext->period_r ? ext->period_r : (uint64_t)pre->rows + post->rows - (pre->rows && post->rows ? 1u : 0u);
+    const uint64_t cols = ext->period_c ? ext->period_c : (uint64_t)pre->cols + post->cols - (pre->cols && post->cols ? 1u : 0u);
+    if (!s.table) return fail(SNN_ERR_BAD_ARG, where + "table is null: SNN_WEIGHT_DISPLACEMENT reads its weights from it");
+    if (s.table_rows != rows)
+        return fail(SNN_ERR_BAD_ARG, where + "table_rows: " + std::to_string(s.table_rows) + " given, these lattices and flags take " + std::to_string(rows));
+    if (s.table_cols != cols)
+        return fail(SNN_ERR_BAD_ARG, where + "table_cols: " + std::to_string(s.table_cols) + " given, these lattices and flags take " + std::to_string(cols));
+    for (uint64_t k = 0; k < rows * cols; ++k)
+        if (s.table[k] == s.table[k] && s.table[k] - s.table[k] != 0.0f)
+            return fail(SNN_ERR_BAD_ARG, where + "table: entry " + std::to_string(k) + " is infinite (a weight is finite; NaN marks the pairs without an edge)");
+    ext->table_cols = s.table_cols;
+    return SNN_OK;
+}
+
+// the table of a checked spec in a device buffer of the handle's allocator (the caller's dev_ptr frees it); ext->table points at it
+static int connect_spec_upload(snn_network *net, const snn_connect_spec &s, ConnectSpecExt *ext, dev_ptr<float> *table_d)
+{
+    if (s.record.weight_rule != CONNECT_DISPLACEMENT) return SNN_OK;
+    const size_t bytes = (size_t)s.table_rows * s.table_cols * 4;
+    HIP_TRY(snn_malloc(table_d, std::max<size_t>(bytes, 256)), SNN_ERR_BUFFER_CREATE);
+    if (bytes) HIP_TRY(copy_sync(net, table_d->get(), s.table, bytes, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+    ext->table = table_d->get();
+    return SNN_OK;
+}
+
+// snn_connect_by_rule and snn_connect_by_spec: one body.  A plain spec (no table, no distance on a ring) launches k_connect_rule.
+static int connect_dense(snn_network_t *net, const snn_connect_spec &s, uint32_t weight_rules)
 {
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
     if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
     if (net->csr) return fail(SNN_ERR_BAD_STATE, "connecting by rule is for dense handles only: this handle holds a sparse graph");
+    const snn_connect_record &r = s.record;
     const LatticeInfo *pre = nullptr, *post = nullptr;
-    TRY(connect_check(net, "", pre_id, post_id, rule, probability, weight_rule, w_lo, w_hi, &pre, &post));
+    ConnectSpecExt x{};
+    if (weight_rules == CONNECT_RULE_WEIGHTS)
+        TRY(connect_check(net, "", r.pre_id, r.post_id, r.rule, r.probability, r.weight_rule, r.w_lo, r.w_hi, &pre, &post, CONNECT_RULE_WEIGHTS));
+    else
+        TRY(connect_spec_check(net, "", s, &pre, &post, &x));
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
     TRY(end_run(net));                     // a deferred reward-modulated update belongs to the OLD weights: apply it first
+    dev_ptr<float> table_d;                // (freed when the call returns; a failure here leaves the graph as it was)
+    TRY(connect_spec_upload(net, s, &x, &table_d));
     net->cross_checked = false;
     net->cache.counts_dirty = true;        // stale from here on, whichever way the call ends (as graph_rows_io marks them on every exit of a set)
     w24_invalidate(net);
@@ -368,24 +417,44 @@ int snn_connect_by_rule(snn_network_t *net, uint32_t pre_id, uint32_t post_id, u
         a.col0 = c_begin - net->q0; a.n_cols = c_end - c_begin; a.post_i0 = c_begin - post->first;
         a.post_cols = post->cols; a.post_count = post->count;
         a.pre_first = pre->first; a.pre_count = pre->count; a.pre_rows = pre->rows; a.pre_cols = pre->cols;
-        a.extent = extent; a.probability = probability; a.edge_seed = edge_seed; a.weight_seed = weight_seed;
-        a.w_lo = w_lo; a.w_hi = w_hi;
+        a.extent = r.extent; a.probability = r.probability; a.edge_seed = r.edge_seed; a.weight_seed = r.weight_seed;
+        a.w_lo = r.w_lo; a.w_hi = r.w_hi;
         const uint32_t groups = ((a.pre_first + a.pre_count - 1u) >> 2) - (a.pre_first >> 2) + 1u;
         const uint32_t blocks_x = (a.col0 + a.n_cols - (a.col0 & ~63u) + 255u) / 256u;
+        const dim3 grid(blocks_x, std::min<uint32_t>(groups, 4096));
+        const bool thin = r.probability < 1.0f, self = r.self_edges != 0, wrap = x.period_r || x.period_c;
         // (probability <= 0: the draw is made and never succeeds)
-        hipLaunchKernelGGL(connect_kernel((int)rule, (int)weight_rule, probability < 1.0f, self_edges != 0),
-                           dim3(blocks_x, std::min<uint32_t>(groups, 4096)), dim3(256), 0, net->stream, a);
+        if (connect_spec_is_plain((int)r.rule, (int)r.weight_rule, wrap))
+            hipLaunchKernelGGL(connect_kernel((int)r.rule, (int)r.weight_rule, thin, self), grid, dim3(256), 0, net->stream, a);
+        else
+            hipLaunchKernelGGL(connect_spec_kernel((int)r.rule, (int)r.weight_rule, wrap, thin, self), grid, dim3(256), 0, net->stream,
+                               ConnectSpecArgs{a, x});
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
         // a replaced edge starts with a fresh TraceRSTDP; the other blocks keep theirs
         for (float *m : {net->trace.get(), net->pending.get(), net->edge_counter.get()})
             if (m) {
-                hipLaunchKernelGGL(k_connect_clear, dim3(blocks_x, std::min<uint32_t>(groups, 4096)), dim3(256), 0,
-                                   net->stream, m, net->ld, a.col0, a.n_cols, a.pre_first, a.pre_count);
+                hipLaunchKernelGGL(k_connect_clear, grid, dim3(256), 0, net->stream, m, net->ld, a.col0, a.n_cols, a.pre_first, a.pre_count);
                 HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
             }
         HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
     }
     return SNN_OK;
+}
+
+int snn_connect_by_rule(snn_network_t *net, uint32_t pre_id, uint32_t post_id, uint32_t rule, uint32_t extent,
+                        int self_edges, float probability, uint64_t edge_seed, uint32_t weight_rule, float w_lo,
+                        float w_hi, uint64_t weight_seed) ABI_TRY
+{
+    snn_connect_spec s{};
+    s.record = snn_connect_record{pre_id, post_id, rule, extent, self_edges, probability, edge_seed, weight_rule, w_lo, w_hi, weight_seed};
+    return connect_dense(net, s, CONNECT_RULE_WEIGHTS);
+}
+ABI_CATCH
+
+int snn_connect_by_spec(snn_network_t *net, const snn_connect_spec *spec) ABI_TRY
+{
+    if (!spec) return fail(SNN_ERR_BAD_ARG, "spec is null");
+    return connect_dense(net, *spec, CONNECT_SPEC_WEIGHTS);
 }
 ABI_CATCH
 
@@ -775,19 +844,25 @@ int snn_get_graph_csr_structure(snn_network_t *net, uint64_t *row_ptr, uint32_t 
 }
 ABI_CATCH
 
-int snn_connect_by_rules_csr(snn_network_t *net, const snn_connect_record *records, uint32_t n_records) ABI_TRY
+// snn_connect_by_rules_csr (specs == nullptr: every record plain) and snn_connect_by_specs_csr (records == nullptr): one body
+static int connect_csr(snn_network_t *net, const snn_connect_record *records, const snn_connect_spec *specs, uint32_t n_records)
 {
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
     if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
     if (!net->csr) return fail(SNN_ERR_BAD_STATE, "handle holds a dense graph: connect it with snn_connect_by_rule");
     if (net->block_mode) return fail(SNN_ERR_BAD_STATE, "connecting by rule does not cover shards by lattice (range-set ownership): not covered");
     if (n_records == 0) return SNN_OK;
-    if (!records) return fail(SNN_ERR_BAD_ARG, "records is null");
+    if (!records && !specs) return fail(SNN_ERR_BAD_ARG, "records is null");
     hvec<std::pair<const LatticeInfo *, const LatticeInfo *>> ends(n_records);
+    hvec<ConnectSpecExt> exts(n_records);
     for (uint32_t k = 0; k < n_records; ++k) {
+        const std::string where = "record " + std::to_string(k) + ": ";
+        if (specs) {
+            TRY(connect_spec_check(net, where, specs[k], &ends[k].first, &ends[k].second, &exts[k]));
+            continue;
+        }
         const snn_connect_record &r = records[k];
-        TRY(connect_check(net, "record " + std::to_string(k) + ": ", r.pre_id, r.post_id, r.rule, r.probability, r.weight_rule, r.w_lo,
-                          r.w_hi, &ends[k].first, &ends[k].second));
+        TRY(connect_check(net, where, r.pre_id, r.post_id, r.rule, r.probability, r.weight_rule, r.w_lo, r.w_hi, &ends[k].first, &ends[k].second, CONNECT_RULE_WEIGHTS));
     }
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
     TRY(end_run(net));                     // a deferred update belongs to the weights the merge is about to read
@@ -838,7 +913,7 @@ int snn_connect_by_rules_csr(snn_network_t *net, const snn_connect_record *recor
     }
     // ---- record by record: count, scan, check the total, fill, swap ----
     for (uint32_t k = 0; k < n_records; ++k) {
-        const snn_connect_record &r = records[k];
+        const snn_connect_record &r = specs ? specs[k].record : records[k];
         const LatticeInfo *lp = ends[k].first, *lq = ends[k].second;
         // the block's rows this handle owns, as local rows (the dense form: its columns)
         const uint32_t c_begin = std::max(lq->first, net->q0), c_end = std::min(lq->first + lq->count, net->q0 + n);
@@ -854,9 +929,16 @@ int snn_connect_by_rules_csr(snn_network_t *net, const snn_connect_record *recor
         a.window = connect_window_extent(r.rule, r.extent, std::max(std::max(lp->rows, lp->cols), std::max(lq->rows, lq->cols)));
         a.old_ptr = ptr[cur]; a.old_pre = pre[cur]; a.old_w = w[cur];
         a.new_len = len_d;
-        const bool thin = r.probability < 1.0f, self = r.self_edges != 0;
+        const bool thin = r.probability < 1.0f, self = r.self_edges != 0, wrap = exts[k].period_r || exts[k].period_c;
+        const bool plain = connect_spec_is_plain((int)r.rule, (int)r.weight_rule, wrap);
+        dev_ptr<float> table_d;                        // (read by both passes; freed after the wait that ends this record)
+        if (specs) TRY(connect_spec_upload(net, specs[k], &exts[k], &table_d));
         const dim3 grid(std::min<uint32_t>((n + 3u) / 4u, 16384u));
-        hipLaunchKernelGGL(connect_csr_kernel<false>((int)r.rule, (int)r.weight_rule, thin, self), grid, dim3(256), 0, net->stream, a);
+        if (plain)
+            hipLaunchKernelGGL(connect_csr_kernel<false>((int)r.rule, (int)r.weight_rule, thin, self), grid, dim3(256), 0, net->stream, a);
+        else
+            hipLaunchKernelGGL(connect_csr_spec_kernel<false>((int)r.rule, (int)r.weight_rule, wrap, thin, self), grid, dim3(256), 0, net->stream,
+                               ConnectCsrSpecArgs{a, exts[k]});
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
         uint64_t total = 0;
         TRY(scan(len_d, ptr[cur ^ 1], &total));
@@ -866,7 +948,11 @@ int snn_connect_by_rules_csr(snn_network_t *net, const snn_connect_record *recor
         TRY(sized(&pre[cur ^ 1], total * 4));
         TRY(sized(&w[cur ^ 1], total * 4));
         a.new_ptr = ptr[cur ^ 1]; a.new_pre = pre[cur ^ 1]; a.new_w = w[cur ^ 1];
-        hipLaunchKernelGGL(connect_csr_kernel<true>((int)r.rule, (int)r.weight_rule, thin, self), grid, dim3(256), 0, net->stream, a);
+        if (plain)
+            hipLaunchKernelGGL(connect_csr_kernel<true>((int)r.rule, (int)r.weight_rule, thin, self), grid, dim3(256), 0, net->stream, a);
+        else
+            hipLaunchKernelGGL(connect_csr_spec_kernel<true>((int)r.rule, (int)r.weight_rule, wrap, thin, self), grid, dim3(256), 0, net->stream,
+                               ConnectCsrSpecArgs{a, exts[k]});
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
         HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);      // (the set just read is freed when it is next sized)
         cur ^= 1;
@@ -887,6 +973,17 @@ int snn_connect_by_rules_csr(snn_network_t *net, const snn_connect_record *recor
     uint32_t no_pre = 0;
     float no_w = 0.0f;
     return set_graph_csr_impl(net, ptr64.data(), nnz ? pre_h.data() : &no_pre, nnz ? w_h.data() : &no_w, nnz);
+}
+
+int snn_connect_by_rules_csr(snn_network_t *net, const snn_connect_record *records, uint32_t n_records) ABI_TRY
+{
+    return connect_csr(net, records, nullptr, n_records);
+}
+ABI_CATCH
+
+int snn_connect_by_specs_csr(snn_network_t *net, const snn_connect_spec *specs, uint32_t n_specs) ABI_TRY
+{
+    return connect_csr(net, nullptr, specs, n_specs);
 }
 ABI_CATCH
 

@@ -635,6 +635,10 @@ public:
                                   w_lo, w_hi, weight_seed));
     }
 
+    // The same with wrap-around distances and / or weights from a displacement table (snn_connect_by_spec): spec.record names the
+    // two lattices; the table is read during the call only.
+    void connect(const snn_connect_spec &spec) { check(snn_connect_by_spec(h_, &spec)); }
+
     // The Graph trait on the device matrix (graph/mod.rs:42-72) by interleaved global index, dense handles: snn_graph_lookup /
     // snn_graph_edit for one pair, snn_graph_incoming / snn_graph_outgoing as ascending (index, weight) lists.  Edits change the
     // device only; sync() brings them into `network`.
@@ -659,6 +663,11 @@ public:
     void connect_sparse(const std::vector<snn_connect_record> &records)
     {
         check(snn_connect_by_rules_csr(h_, records.data(), (uint32_t)records.size()));
+    }
+    // ... and with the extension of snn_connect_spec (snn_connect_by_specs_csr): wrapped windows, displacement tables
+    void connect_sparse(const std::vector<snn_connect_spec> &specs)
+    {
+        check(snn_connect_by_specs_csr(h_, specs.data(), (uint32_t)specs.size()));
     }
     // (row_ptr, pre_index) of a sparse handle's graph, rows = neurons in ascending index; csr_weights() in the same edge order
     std::pair<std::vector<uint64_t>, std::vector<uint32_t>> csr_structure()

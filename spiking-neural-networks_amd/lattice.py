@@ -18,7 +18,7 @@ from .network import (CUSTOM, NT_CUSTOM, RC_CUSTOM, REFRACTORINESS_CUSTOM, ST_CU
                       DeviceNetwork, HODGKIN_HUXLEY, IZHIKEVICH, LIF, QUADRATIC_INTEGRATE_AND_FIRE, SIMPLE_LIF,
                       ADAPTIVE_LIF, ADAPTIVE_EXP_LIF, LEAKY_IZHIKEVICH,
                       NT_APPROXIMATE, NT_DESTEXHE,
-                      RC_APPROXIMATE, RC_DESTEXHE, ST_NONE, ST_POISSON, ST_RATE, ConnectionRule, WeightRule)
+                      RC_APPROXIMATE, RC_DESTEXHE, ST_NONE, ST_POISSON, ST_RATE, ConnectionRule, WeightRule, check_rule_pair, rule_pairs)
 
 
 def _rule_records(rule, weight):
@@ -29,16 +29,19 @@ def _rule_records(rule, weight):
         return None
     if weight is not None and not isinstance(weight, WeightRule):
         raise TypeError("a ConnectionRule goes with a WeightRule (or None: every edge weighs 1), not with a closure")
-    return rule, (WeightRule.constant(1.0) if weight is None else weight)
+    weight = WeightRule.constant(1.0) if weight is None else weight
+    check_rule_pair(rule, weight)
+    return rule, weight
 
 
 def _rule_graph(rule, weight, pre_shape, post_shape):
-    """(mask, weights) of a ConnectionRule / WeightRule pair on two grids: what snn_connect_by_rule writes on the device,
-    from the records' host twins.  None when the arguments are the reference's two closures."""
+    """(mask, weights) of a ConnectionRule / WeightRule pair on two grids: what snn_connect_by_spec writes on the device,
+    from the records' host twins (a NaN of a displacement table is an absent edge).  None when the arguments are the
+    reference's two closures."""
     records = _rule_records(rule, weight)
     if records is None:
         return None
-    return records[0].mask(pre_shape, post_shape), records[1].values(pre_shape, post_shape)
+    return rule_pairs(*records, pre_shape, post_shape)
 
 
 class IonotropicNeurotransmitterType(enum.IntEnum):      # iterate_and_spike/mod.rs:1068-1073
@@ -514,8 +517,7 @@ class Lattice:
         elif self._rule is None:
             w, c = np.zeros((n, n), np.float32), np.zeros((n, n), np.uint32)
         else:
-            on = self._rule[0].mask(shape, shape)
-            w = np.where(on, self._rule[1].values(shape, shape), np.float32(0)).astype(np.float32)
+            on, w = rule_pairs(*self._rule, shape, shape)
             c = on.astype(np.uint32)
         self._weights, self._connections, self._rule = w, c, None
 
@@ -628,7 +630,7 @@ class Lattice:
         if self._rule is None:
             size = (n if pre_index is None else len(pre_index), n if post_index is None else len(post_index))
             return np.zeros(size, bool), np.zeros(size, np.float32)
-        return (self._rule[0].mask(shape, shape, pre_index, post_index), self._rule[1].values(shape, shape, pre_index, post_index))
+        return rule_pairs(*self._rule, shape, shape, pre_index, post_index)
 
     def get_incoming_connections(self, position):
         j = self._index(position)

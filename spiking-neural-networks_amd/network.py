@@ -43,7 +43,29 @@ def _out(shape, dtype=np.float32):
 _PTR = {"f32": _lib.f32p, "u32": _lib.u32p, "i32": _lib.i32p}
 
 RULE_ALL, RULE_CHEBYSHEV, RULE_EUCLIDEAN, RULE_SAME_POSITION = 0, 1, 2, 3      # snn_connection_rule
-WEIGHT_CONSTANT, WEIGHT_UNIFORM = 0, 1                                         # snn_weight_rule
+WEIGHT_CONSTANT, WEIGHT_UNIFORM, WEIGHT_DISPLACEMENT = 0, 1, 2                  # snn_weight_rule
+WRAP_ROWS, WRAP_COLS = 1, 2                                                    # snn_connect_spec.wrap
+
+
+def _wrap_flags(wrap):
+    """wrap=True / False / (rows, cols) as WRAP_ROWS | WRAP_COLS"""
+    if isinstance(wrap, (bool, np.bool_)):
+        return (WRAP_ROWS | WRAP_COLS) if wrap else 0
+    try:
+        rows, cols = wrap
+    except (TypeError, ValueError):
+        raise ValueError(f"wrap is True, False or (rows, cols), not {wrap!r}") from None
+    return (WRAP_ROWS if rows else 0) | (WRAP_COLS if cols else 0)
+
+
+def _wrap_pair(flags):
+    return bool(flags & WRAP_ROWS), bool(flags & WRAP_COLS)
+
+
+def _periods(flags, pre_shape, post_shape):
+    """(P_r, P_c): the ring a wrapped dimension closes on -- the larger of the two grids' sizes -- and 0 where it does not wrap"""
+    return (max(pre_shape[0], post_shape[0]) if flags & WRAP_ROWS else 0,
+            max(pre_shape[1], post_shape[1]) if flags & WRAP_COLS else 0)
 
 
 def _pair_grid(pre_shape, post_shape, pre_index=None, post_index=None):
@@ -76,9 +98,10 @@ class ConnectionRule:
     connect(&|x, y| ...) (neuron/mod.rs:1134-1157, 1845-1935), as data the device evaluates (snn_connect_by_rule of
     include/snn_amd.h, whose wording `mask` restates in numpy).  kind RULE_ALL | RULE_CHEBYSHEV (max(dr, dc) <= extent) |
     RULE_EUCLIDEAN (dr^2 + dc^2 <= extent, the squared radius) | RULE_SAME_POSITION; self_edges=False is `x != y`;
-    0 < probability < 1 adds a coin flip per pair drawn from `seed`."""
+    0 < probability < 1 adds a coin flip per pair drawn from `seed`.  wrap=True, or (rows, cols): the distances of the two radius
+    rules are taken on a ring of max(pre, post) rows / columns (snn_connect_by_spec)."""
 
-    def __init__(self, kind, extent=0, self_edges=True, probability=1.0, seed=0):
+    def __init__(self, kind, extent=0, self_edges=True, probability=1.0, seed=0, wrap=False):
         if kind not in (RULE_ALL, RULE_CHEBYSHEV, RULE_EUCLIDEAN, RULE_SAME_POSITION):
             raise ValueError(f"unknown connection rule {kind!r}")
         if not 0 <= int(extent) < 2 ** 32 or not 0 <= int(seed) < 2 ** 64:
@@ -87,6 +110,7 @@ class ConnectionRule:
             raise ValueError("probability is NaN")
         self.kind, self.extent, self.self_edges = int(kind), int(extent), bool(self_edges)
         self.probability, self.seed = float(probability), int(seed)
+        self.wrap = _wrap_flags(wrap)
 
     @classmethod
     def all_to_all(cls, **kw):
@@ -105,23 +129,30 @@ class ConnectionRule:
         return cls(RULE_SAME_POSITION, **kw)
 
     def __repr__(self):
+        wrap = f", wrap={_wrap_pair(self.wrap)}" if self.wrap else ""
         return (f"ConnectionRule(kind={self.kind}, extent={self.extent}, self_edges={self.self_edges}, "
-                f"probability={self.probability}, seed={self.seed})")
+                f"probability={self.probability}, seed={self.seed}{wrap})")
 
     def mask(self, pre_shape, post_shape, pre_index=None, post_index=None):
         """bool[n_pre, n_post]: the pairs the device call connects, for grids (rows, cols); with pre_index / post_index (lattice-local
         indices) those rows / columns of it only"""
         ra, ca, rb, cb, idx = _pair_grid(pre_shape, post_shape, pre_index, post_index)
         dr, dc = np.abs(ra - rb), np.abs(ca - cb)
+        same = (dr | dc) == 0
+        p_r, p_c = _periods(self.wrap, pre_shape, post_shape)
+        if p_r:
+            dr = np.minimum(dr, p_r - dr)
+        if p_c:
+            dc = np.minimum(dc, p_c - dc)
         on = np.ones(idx.shape, bool)
         if self.kind == RULE_CHEBYSHEV:
             on = np.maximum(dr, dc) <= self.extent
         elif self.kind == RULE_EUCLIDEAN:
             on = dr * dr + dc * dc <= self.extent
         elif self.kind == RULE_SAME_POSITION:
-            on = (dr | dc) == 0
+            on = same
         if not self.self_edges:
-            on = on & ((dr | dc) != 0)
+            on = on & ~same
         p = np.float32(self.probability)
         if p <= 0:
             on = np.zeros(idx.shape, bool)
@@ -131,11 +162,14 @@ class ConnectionRule:
 
 
 class WeightRule:
-    """The weight of every pair a ConnectionRule connects: WeightRule.constant(w), or WeightRule.uniform(lo, hi, seed) =
-    lo + (hi - lo) * u24(hash(seed, idx)) in float32 -- synthetic.uniform on the pair index"""
+    """The weight of every pair a ConnectionRule connects: WeightRule.constant(w), WeightRule.uniform(lo, hi, seed) =
+    lo + (hi - lo) * u24(hash(seed, idx)) in float32 -- synthetic.uniform on the pair index -- or
+    WeightRule.displacement(table, wrap): the entry of a 2-D float32 table for the displacement post - pre (a convolution kernel;
+    on a ring or torus with wrap), NaN where that displacement carries no edge.  The table's shape follows from the two grids:
+    per dimension max(pre, post) where it wraps, pre + post - 1 where it does not (SNN_WEIGHT_DISPLACEMENT of include/snn_amd.h)."""
 
-    def __init__(self, kind, lo, hi=0.0, seed=0):
-        if kind not in (WEIGHT_CONSTANT, WEIGHT_UNIFORM):
+    def __init__(self, kind, lo=0.0, hi=0.0, seed=0, table=None, wrap=False):
+        if kind not in (WEIGHT_CONSTANT, WEIGHT_UNIFORM, WEIGHT_DISPLACEMENT):
             raise ValueError(f"unknown weight rule {kind!r}")
         if not (np.isfinite(np.float32(lo)) and np.isfinite(np.float32(hi))):
             raise ValueError("weights must be finite (NaN marks the absent edge)")
@@ -146,6 +180,16 @@ class WeightRule:
         if not 0 <= int(seed) < 2 ** 64:
             raise ValueError("seed is a uint64")
         self.kind, self.lo, self.hi, self.seed = int(kind), float(lo), float(hi), int(seed)
+        self.table, self.wrap = None, _wrap_flags(wrap)
+        if kind == WEIGHT_DISPLACEMENT:
+            table = np.ascontiguousarray(table, dtype=np.float32)
+            if table.ndim != 2:
+                raise ValueError("the displacement table is 2-D: [row displacement, column displacement]")
+            if np.isinf(table).any():
+                raise ValueError("the displacement table holds an infinite weight (NaN marks a displacement without an edge)")
+            self.table = table
+        elif table is not None:
+            raise ValueError("a table goes with WEIGHT_DISPLACEMENT")
 
     @classmethod
     def constant(cls, w):
@@ -155,17 +199,74 @@ class WeightRule:
     def uniform(cls, lo, hi, seed=0):
         return cls(WEIGHT_UNIFORM, lo, hi, seed)
 
+    @classmethod
+    def displacement(cls, table, wrap=False):
+        return cls(WEIGHT_DISPLACEMENT, table=table, wrap=wrap)
+
+    @staticmethod
+    def table_shape(pre_shape, post_shape, wrap=False):
+        """the table two grids take: per dimension the ring's period where it wraps, pre + post - 1 where it does not"""
+        return tuple(p or (a + b - 1) for p, a, b in zip(_periods(_wrap_flags(wrap), pre_shape, post_shape), pre_shape, post_shape))
+
+    @classmethod
+    def from_displacement_function(cls, fn, pre_shape, post_shape, wrap=False):
+        """the table of a weight that depends on the displacement between the two positions only -- the reference's attractor
+        experiments: connect(lambda x, y: True, w) -- filled by calling fn(pre_pos, post_pos) ONCE per displacement, on a pair of
+        positions that has it; np.float32(result), or NaN (no edge) where fn returns None"""
+        flags = _wrap_flags(wrap)
+        periods = _periods(flags, pre_shape, post_shape)
+
+        def pair(k, period, n_pre, n_post):
+            """(pre, post) coordinates whose displacement has table index k"""
+            if period:                                  # k = (post - pre) mod period; the grid that spans the ring moves
+                return (0, k) if n_post == period else ((-k) % period, 0)
+            d = k - (n_pre - 1)                         # k = post - pre + (n_pre - 1)
+            return (0, d) if d >= 0 else (-d, 0)
+        table = np.empty(cls.table_shape(pre_shape, post_shape, wrap), np.float32)
+        for u in range(table.shape[0]):
+            ra, rb = pair(u, periods[0], pre_shape[0], post_shape[0])
+            for v in range(table.shape[1]):
+                ca, cb = pair(v, periods[1], pre_shape[1], post_shape[1])
+                w = fn((ra, ca), (rb, cb))
+                table[u, v] = np.nan if w is None else np.float32(w)
+        return cls.displacement(table, wrap)
+
     def __repr__(self):
+        if self.kind == WEIGHT_DISPLACEMENT:
+            return f"WeightRule(kind={self.kind}, table={self.table.shape}, wrap={_wrap_pair(self.wrap)})"
         return f"WeightRule(kind={self.kind}, lo={self.lo}, hi={self.hi}, seed={self.seed})"
 
     def values(self, pre_shape, post_shape, pre_index=None, post_index=None):
-        """float32[n_pre, n_post]: the weight the device call gives each pair (whether or not the rule connects it); with
-        pre_index / post_index (lattice-local indices) those rows / columns of it only"""
-        idx = _pair_grid(pre_shape, post_shape, pre_index, post_index)[4]
+        """float32[n_pre, n_post]: the weight the device call gives each pair (whether or not the rule connects it; NaN where the
+        displacement table says None); with pre_index / post_index (lattice-local indices) those rows / columns of it only"""
+        ra, ca, rb, cb, idx = _pair_grid(pre_shape, post_shape, pre_index, post_index)
+        if self.kind == WEIGHT_DISPLACEMENT:
+            if self.table.shape != self.table_shape(pre_shape, post_shape, _wrap_pair(self.wrap)):
+                raise ValueError(f"a displacement table of shape {self.table.shape} does not fit grids {tuple(pre_shape)} -> {tuple(post_shape)}: "
+                                 f"they take {self.table_shape(pre_shape, post_shape, _wrap_pair(self.wrap))}")
+            p_r, p_c = _periods(self.wrap, pre_shape, post_shape)
+            u = (rb - ra) % p_r if p_r else rb - ra + (pre_shape[0] - 1)
+            v = (cb - ca) % p_c if p_c else cb - ca + (pre_shape[1] - 1)
+            return self.table[u, v]
         lo, hi = np.float32(self.lo), np.float32(self.hi)
         if self.kind == WEIGHT_CONSTANT:
             return np.full(idx.shape, lo, np.float32)
         return (lo + (hi - lo) * _u24(self.seed, idx)).astype(np.float32)
+
+
+def check_rule_pair(rule, weight):
+    """a displacement table is indexed on the rings its rule measures distances on: the two wrap settings must agree"""
+    if weight.kind == WEIGHT_DISPLACEMENT and weight.wrap != rule.wrap:
+        raise ValueError(f"the displacement table was built with wrap={_wrap_pair(weight.wrap)}, its rule with wrap={_wrap_pair(rule.wrap)}")
+
+
+def rule_pairs(rule, weight, pre_shape, post_shape, pre_index=None, post_index=None):
+    """(connected bool, weights float32, 0 where there is no edge) [n_pre, n_post]: the graph one connect record writes on the
+    device, from the records' host twins -- a NaN of the displacement table is an absent edge"""
+    check_rule_pair(rule, weight)
+    on, w = rule.mask(pre_shape, post_shape, pre_index, post_index), weight.values(pre_shape, post_shape, pre_index, post_index)
+    on = on & ~np.isnan(w)
+    return on, np.where(on, w, np.float32(0)).astype(np.float32)
 
 
 class DeviceNetwork:
@@ -367,32 +468,36 @@ class DeviceNetwork:
     def fill_graph_synthetic(self, seed, lo, hi, with_diagonal=False):
         self._check(self._L.snn_fill_graph_synthetic(self._h, seed, lo, hi, int(with_diagonal)))
 
-    def connect_by_rule(self, pre_id, post_id, rule, weight=None):
-        """the reference's connect(...) between lattice `pre_id` and neuron lattice `post_id` (the same id: internally), evaluated
-        on the device (snn_connect_by_rule): `rule` a ConnectionRule, `weight` a WeightRule (None: every edge weighs 1).
-        rule.mask / weight.values are the same graph on the host."""
+    def _connect_spec(self, pre_id, post_id, rule, weight, what):
+        """snn_connect_spec of one (ConnectionRule, WeightRule or None) pair; the spec points into weight.table"""
         weight = WeightRule.constant(1.0) if weight is None else weight
         if not isinstance(rule, ConnectionRule) or not isinstance(weight, WeightRule):
-            raise TypeError("connect_by_rule takes a ConnectionRule and a WeightRule")
-        self._check(self._L.snn_connect_by_rule(self._h, pre_id, post_id, rule.kind, rule.extent, int(rule.self_edges),
-                                               rule.probability, rule.seed, weight.kind, weight.lo, weight.hi, weight.seed))
+            raise TypeError(f"{what} takes a ConnectionRule and a WeightRule")
+        check_rule_pair(rule, weight)
+        record = _lib.ConnectRecord(int(pre_id), int(post_id), rule.kind, rule.extent, int(rule.self_edges), rule.probability,
+                                    rule.seed, weight.kind, weight.lo, weight.hi, weight.seed)
+        if weight.kind != WEIGHT_DISPLACEMENT:
+            return _lib.ConnectSpec(record, rule.wrap, 0, 0, None)
+        return _lib.ConnectSpec(record, rule.wrap, weight.table.shape[0], weight.table.shape[1], weight.table.ctypes.data_as(_lib.f32p))
+
+    def connect_by_rule(self, pre_id, post_id, rule, weight=None):
+        """the reference's connect(...) between lattice `pre_id` and neuron lattice `post_id` (the same id: internally), evaluated
+        on the device (snn_connect_by_spec): `rule` a ConnectionRule, `weight` a WeightRule (None: every edge weighs 1).
+        rule.mask / weight.values are the same graph on the host (rule_pairs: a NaN of a displacement table is no edge)."""
+        spec = self._connect_spec(pre_id, post_id, rule, weight, "connect_by_rule")
+        self._check(self._L.snn_connect_by_spec(self._h, C.byref(spec)))
 
     def connect_sparse(self, plan):
-        """connect(...) on a sparse handle, the graph merged on the device (snn_connect_by_rules_csr): `plan` is a list of
+        """connect(...) on a sparse handle, the graph merged on the device (snn_connect_by_specs_csr): `plan` is a list of
         (pre_id, post_id, ConnectionRule, WeightRule or None), applied in order and committed once.  Every edge outside the plan's
         blocks keeps its current weight; traces, dw and counters of the whole graph restart at 0.  The committed edge order is
-        graph_csr_structure()'s."""
-        records = (_lib.ConnectRecord * max(len(plan), 1))()
+        graph_csr_structure()'s.  A displacement table visits the candidates of its rule: on a large handle give it a radius."""
+        specs = (_lib.ConnectSpec * max(len(plan), 1))()
         for k, entry in enumerate(plan):
             if not isinstance(entry, (tuple, list)) or len(entry) != 4:
                 raise TypeError(f"plan[{k}] must be (pre_id, post_id, ConnectionRule, WeightRule or None)")
-            pre_id, post_id, rule, weight = entry
-            weight = WeightRule.constant(1.0) if weight is None else weight
-            if not isinstance(rule, ConnectionRule) or not isinstance(weight, WeightRule):
-                raise TypeError(f"plan[{k}]: connect_sparse takes a ConnectionRule and a WeightRule")
-            records[k] = _lib.ConnectRecord(int(pre_id), int(post_id), rule.kind, rule.extent, int(rule.self_edges), rule.probability,
-                                            rule.seed, weight.kind, weight.lo, weight.hi, weight.seed)
-        self._check(self._L.snn_connect_by_rules_csr(self._h, records, len(plan)))
+            specs[k] = self._connect_spec(*entry, f"plan[{k}]: connect_sparse")
+        self._check(self._L.snn_connect_by_specs_csr(self._h, specs, len(plan)))
         nnz = C.c_uint64()
         self._check(self._L.snn_graph_csr_nnz(self._h, C.byref(nnz)))
         self._nnz = int(nnz.value)
