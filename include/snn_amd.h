@@ -248,6 +248,34 @@ int snn_get_graph_csr(snn_network_t *net, float *weights, uint64_t nnz);
 int snn_graph_csr_nnz(snn_network_t *net, uint64_t *nnz);
 int snn_get_graph_csr_structure(snn_network_t *net, uint64_t *row_ptr, uint32_t *pre_index, uint64_t nnz);
 
+/* The Graph trait on a SPARSE handle (graph/mod.rs:42-72: lookup_weight, edit_weight, get_incoming_connections,
+ * get_outgoing_connections): the four snn_graph_* calls above, for a handle whose graph is CSR.  Answered on the device from the
+ * arrays snn_set_graph_csr / snn_connect_by_rules_csr left there -- a binary search of one row per pair, one row, one source of
+ * the transpose; host work and transfers are O(pairs asked for) / O(length of the line), nothing of size nnz is read or built.
+ * As above, word for word: indices are interleaved global indices, pre < n_tot, post < n_neurons; an absent pair reads 0.0f / 0;
+ * lists come back in ASCENDING index order; *count is always set and the lists are written only when capacity >= *count (the
+ * two-call idiom; with *count == 0 the list pointers may be null); every pair of a call is validated before anything is read or
+ * written and snn_last_error names the first offending pair by its position in the call; n == 0 is SNN_OK and touches nothing;
+ * null pointers with n > 0 are SNN_ERR_BAD_ARG; deferred plasticity updates are applied first, so the four agree bit for bit
+ * with snn_get_graph_csr at that moment.
+ * What differs: the STRUCTURE IS FIXED, so snn_graph_csr_edit edits the weights of stored edges only.  connected[k] != 0 on a
+ * stored edge sets its weight; connected[k] == 0 on an absent pair is a no-op; connected[k] != 0 on an absent pair and
+ * connected[k] == 0 on a stored edge are SNN_ERR_BAD_ARG (the message names the pair; snn_connect_by_rules_csr /
+ * snn_set_graph_csr are what changes a structure) -- every occurrence of a pair is held to this, found in one resolve pass over
+ * all pairs before anything is written.  A connected NaN weight is refused as above.  Of a pair listed more than once the last
+ * occurrence wins.  After an accepted edit snn_get_graph_csr returns the edited values and nothing else has changed; the step
+ * image is packed again before the next step that reads it; traces, dw and counters of the edited edges restart at 0, those of
+ * all others stay.
+ * Unsharded sparse handles and contiguous shards: a shard answers for the posts it owns (others: SNN_ERR_BAD_ARG, as above) and
+ * snn_graph_csr_outgoing lists its owned rows only, as global indices.  A sparse handle that holds no graph yet answers "absent"
+ * everywhere and count 0.  SNN_ERR_BAD_STATE: a shard by lattice (range-set ownership: not covered), a dense handle (the four
+ * calls above are its), a handle that is not finalized. */
+int snn_graph_csr_lookup(snn_network_t *net, const uint32_t *pre, const uint32_t *post, size_t n, float *weights, uint8_t *connected);
+int snn_graph_csr_edit(snn_network_t *net, const uint32_t *pre, const uint32_t *post, const float *weights, const uint8_t *connected,
+                       size_t n);
+int snn_graph_csr_incoming(snn_network_t *net, uint32_t post, uint32_t *pre_index, float *weights, uint64_t capacity, uint64_t *count);
+int snn_graph_csr_outgoing(snn_network_t *net, uint32_t pre, uint32_t *post_index, float *weights, uint64_t capacity, uint64_t *count);
+
 /* Connect by rule on SPARSE handles: the CSR graph is built on the device.  A record holds the arguments of snn_connect_by_rule
  * after the handle, with the same meaning, validation and per-pair formulas (pair index, predicate, draw, weight).  The records
  * are applied in the order given, as if by successive calls (a later record for the same (pre, post) pair wins), and committed

@@ -626,6 +626,216 @@ int snn_graph_outgoing(snn_network_t *net, uint32_t pre, uint32_t *post_index, f
 }
 ABI_CATCH
 
+// ---- the Graph trait on a sparse handle (graph/mod.rs:42-72), on the SELL-64 arrays and the transpose as they lie on the device:
+// no table of size nnz is read, built or moved by any of the four (no edge_slot_host, no download of the SELL arrays) ----
+static int graph_csr_begin(const snn_network *net)
+{
+    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
+    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
+    if (!net->csr)
+        return fail(SNN_ERR_BAD_STATE, "handle holds a dense graph: ask it with snn_graph_lookup / snn_graph_edit / snn_graph_incoming / "
+                                       "snn_graph_outgoing");
+    if (net->block_mode) return fail(SNN_ERR_BAD_STATE, "the graph queries do not cover shards by lattice (range-set ownership): not covered");
+    return SNN_OK;
+}
+static std::string graph_csr_pair(size_t k, uint32_t pre, uint32_t post)
+{
+    return "pair " + std::to_string(k) + " (pre " + std::to_string(pre) + ", post " + std::to_string(post) + ")";
+}
+static int graph_csr_fixed(size_t k, uint32_t pre, uint32_t post, bool connect)
+{
+    return fail(SNN_ERR_BAD_ARG, graph_csr_pair(k, pre, post) + (connect ? ": no stored edge, and an edit cannot connect it" : ": a stored edge, and an edit cannot remove it") +
+                                     ": the structure of a sparse graph is fixed (snn_connect_by_rules_csr / snn_set_graph_csr replace it).  "
+                                     "Nothing of this call was applied");
+}
+
+int snn_graph_csr_lookup(snn_network_t *net, const uint32_t *pre, const uint32_t *post, size_t n, float *weights, uint8_t *connected) ABI_TRY
+{
+    TRY(graph_csr_begin(net));
+    if (n == 0) return SNN_OK;
+    if (!pre || !post || !weights || !connected) return fail(SNN_ERR_BAD_ARG, "null pointer with n > 0");
+    for (size_t k = 0; k < n; ++k)
+        if (pre[k] >= net->n_tot || post[k] - net->q0 >= net->n_loc) return graph_pair_check(net, "pair " + std::to_string(k), pre[k], post[k]);
+    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
+    TRY(end_run(net));                     // deferred STDP / R-STDP updates belong to the weights a lookup sees
+    if (!net->csr_ptr) {                   // no graph set yet: the empty one
+        std::fill(weights, weights + n, 0.0f);
+        std::fill(connected, connected + n, (uint8_t)0);
+        return SNN_OK;
+    }
+    const size_t hop = std::min(n, GRAPH_PAIRS_HOP);
+    dev_ptr<uint32_t> pre_d, post_d;
+    dev_ptr<float> w_d;
+    dev_ptr<uint8_t> c_d;
+    HIP_TRY(snn_malloc(&pre_d, hop * 4), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(&post_d, hop * 4), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(&w_d, hop * 4), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(&c_d, std::max<size_t>(hop, 256)), SNN_ERR_BUFFER_CREATE);
+    for (size_t k = 0; k < n; k += hop) {
+        const uint32_t m = (uint32_t)std::min(hop, n - k);
+        HIP_TRY(copy_sync(net, pre_d, pre + k, (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        HIP_TRY(copy_sync(net, post_d, post + k, (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        hipLaunchKernelGGL(k_graph_csr_find, dim3((m + 255u) / 256u), dim3(256), 0, net->stream, (const uint32_t *)net->csr_ptr,
+                           (const uint32_t *)net->csr_pre, (const float *)net->csr_w, (const uint32_t *)net->csr_row_len, net->q0,
+                           (const uint32_t *)pre_d, (const uint32_t *)post_d, m, (uint32_t *)nullptr, w_d.get(), c_d.get(),
+                           (const uint8_t *)nullptr, 0ull, (unsigned long long *)nullptr);
+        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+        HIP_TRY(copy_sync(net, weights + k, w_d, (size_t)m * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+        HIP_TRY(copy_sync(net, connected + k, c_d, m, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    }
+    return SNN_OK;
+}
+ABI_CATCH
+
+int snn_graph_csr_edit(snn_network_t *net, const uint32_t *pre, const uint32_t *post, const float *weights, const uint8_t *connected,
+                       size_t n) ABI_TRY
+{
+    TRY(graph_csr_begin(net));
+    if (n == 0) return SNN_OK;
+    if (!pre || !post || !weights || !connected) return fail(SNN_ERR_BAD_ARG, "null pointer with n > 0");
+    // every pair is checked before anything is written: a refused call leaves the graph as it was
+    bool ascending = true;                 // strictly, by (pre, post): no pair twice
+    for (size_t k = 0; k < n; ++k) {
+        if (pre[k] >= net->n_tot || post[k] - net->q0 >= net->n_loc) return graph_pair_check(net, "pair " + std::to_string(k), pre[k], post[k]);
+        if (connected[k] && weights[k] != weights[k])
+            return fail(SNN_ERR_BAD_ARG, graph_csr_pair(k, pre[k], post[k]) + ": a connected edge carries a NaN weight; NaN is the absent-edge "
+                                         "sentinel of the dense form, which the sparse form refuses alike (graph/mod.rs:204-213).  Nothing of "
+                                         "this call was applied");
+        if (k && (pre[k] < pre[k - 1] || (pre[k] == pre[k - 1] && post[k] <= post[k - 1]))) ascending = false;
+    }
+    if (!net->csr_ptr) {                   // no graph set yet: every pair is absent, and stays so
+        for (size_t k = 0; k < n; ++k)
+            if (connected[k]) return graph_csr_fixed(k, pre[k], post[k], true);
+        return SNN_OK;
+    }
+    // "as if one after another": the structure never changes, so every occurrence of a pair is held to the rule on its own (the
+    // resolve pass, in the order of the call), and of a pair that occurs more than once the LAST occurrence is written, decided
+    // here -- every entry is written by one thread, whatever the order the threads run in
+    hvec<uint64_t> order;
+    size_t kept = n;
+    if (!ascending) {
+        order.resize(n);
+        for (size_t k = 0; k < n; ++k) order[k] = k;
+        auto key = [&](uint64_t k) { return ((uint64_t)pre[k] << 32) | post[k]; };
+        std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return key(a) != key(b) ? key(a) < key(b) : a < b; });
+        kept = 0;
+        for (size_t k = 0; k < n; ++k)
+            if (k + 1 == n || key(order[k + 1]) != key(order[k])) order[kept++] = order[k];
+    }
+    const size_t hop = std::min(n, GRAPH_PAIRS_HOP);
+    hvec<float> value_h(ascending ? 0 : hop);
+    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
+    TRY(end_run(net));                     // a deferred update belongs to the OLD weights: applied now, it cannot overwrite the edit
+    dev_ptr<uint32_t> pre_d, post_d, slot_d;
+    dev_ptr<uint8_t> want_d;
+    dev_ptr<float> value_d;
+    dev_ptr<unsigned long long> sel_d, bad_d;
+    HIP_TRY(snn_malloc(&pre_d, hop * 4), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(&post_d, hop * 4), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(&want_d, std::max<size_t>(hop, 256)), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(&slot_d, n * 4), SNN_ERR_BUFFER_CREATE);            // the entry of every pair of the call, in its order
+    HIP_TRY(snn_malloc(&value_d, hop * 4), SNN_ERR_BUFFER_CREATE);
+    if (!ascending) HIP_TRY(snn_malloc(&sel_d, hop * 8), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(&bad_d, 256), SNN_ERR_BUFFER_CREATE);
+    if (net->opt.pinned_copies && !net->copy_stage)           // (the staging buffer of copy_sync: allocated before the first write)
+        HIP_TRY(host_malloc(&net->copy_stage, (size_t)8 << 20, hipHostMallocDefault), SNN_ERR_BUFFER_CREATE);
+    // ---- the resolve pass: read only ----
+    unsigned long long bad = GRAPH_CSR_ALL_FINE;
+    HIP_TRY(copy_sync(net, bad_d, &bad, 8, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+    for (size_t k = 0; k < n; k += hop) {
+        const uint32_t m = (uint32_t)std::min(hop, n - k);
+        HIP_TRY(copy_sync(net, pre_d, pre + k, (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        HIP_TRY(copy_sync(net, post_d, post + k, (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        HIP_TRY(copy_sync(net, want_d, connected + k, m, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        hipLaunchKernelGGL(k_graph_csr_find, dim3((m + 255u) / 256u), dim3(256), 0, net->stream, (const uint32_t *)net->csr_ptr,
+                           (const uint32_t *)net->csr_pre, (const float *)net->csr_w, (const uint32_t *)net->csr_row_len, net->q0,
+                           (const uint32_t *)pre_d, (const uint32_t *)post_d, m, slot_d.get() + k, (float *)nullptr, (uint8_t *)nullptr,
+                           (const uint8_t *)want_d, (unsigned long long)k, bad_d.get());
+        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+        HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
+    }
+    HIP_TRY(copy_sync(net, &bad, bad_d, 8, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    if (bad != GRAPH_CSR_ALL_FINE) {
+        if (bad >= n) return fail(SNN_ERR_BAD_STATE, "the resolve pass named a pair the call does not have");
+        return graph_csr_fixed((size_t)bad, pre[bad], post[bad], connected[bad] != 0);
+    }
+    // ---- the write pass ----
+    net->cross_checked = false;
+    net->img_stale = net->img_stale_direct = true;             // the step image's records are packed again before the next image step
+    for (size_t k = 0; k < kept; k += hop) {
+        const uint32_t m = (uint32_t)std::min(hop, kept - k);
+        if (ascending) {
+            HIP_TRY(copy_sync(net, value_d, weights + k, (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        } else {
+            for (uint32_t j = 0; j < m; ++j) value_h[j] = weights[order[k + j]];
+            HIP_TRY(copy_sync(net, value_d, value_h.data(), (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+            HIP_TRY(copy_sync(net, sel_d, order.data() + k, (size_t)m * 8, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        }
+        hipLaunchKernelGGL(k_graph_csr_store, dim3((m + 255u) / 256u), dim3(256), 0, net->stream, net->csr_w.get(), net->trace.get(),
+                           net->pending.get(), net->edge_counter.get(), (const uint32_t *)(ascending ? slot_d.get() + k : slot_d.get()),
+                           (const unsigned long long *)sel_d.get(), (const float *)value_d, m);
+        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+        HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
+    }
+    return SNN_OK;
+}
+ABI_CATCH
+
+// one row of the SELL arrays (incoming) or one source of the transpose (outgoing) as ascending (index, weight) lists: the count
+// is one or two words read from the device, the lists are copied when there is room for them
+static int graph_csr_line(snn_network *net, bool incoming, uint32_t line, uint32_t *index, float *weights, uint64_t capacity, uint64_t *count)
+{
+    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
+    TRY(end_run(net));
+    if (!net->csr_ptr || net->n_loc == 0) return SNN_OK;          // no graph set yet: the empty one
+    uint32_t span[2] = {0, 0};
+    if (incoming) HIP_TRY(copy_sync(net, &span[1], net->csr_row_len.get() + line, 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    else HIP_TRY(copy_sync(net, span, net->csr_t_ptr.get() + line, 8, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    if (span[1] < span[0]) return fail(SNN_ERR_BAD_STATE, "the stored transpose offsets are not monotone");
+    const uint32_t found = span[1] - span[0];
+    *count = found;
+    if (found == 0 || found > capacity) return SNN_OK;
+    if (!index || !weights) return fail(SNN_ERR_BAD_ARG, "null list pointer with capacity >= count > 0");
+    dev_ptr<uint32_t> index_d;
+    dev_ptr<float> w_d;
+    HIP_TRY(snn_malloc(&index_d, std::max<size_t>((size_t)found * 4, 256)), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(&w_d, std::max<size_t>((size_t)found * 4, 256)), SNN_ERR_BUFFER_CREATE);
+    const dim3 grid(std::min<uint32_t>((found + 255u) / 256u, 1024u));
+    if (incoming)
+        hipLaunchKernelGGL(k_graph_csr_row, grid, dim3(256), 0, net->stream, (const uint32_t *)net->csr_ptr, (const uint32_t *)net->csr_pre,
+                           (const float *)net->csr_w, line, found, index_d.get(), w_d.get());
+    else
+        hipLaunchKernelGGL(k_graph_csr_out, grid, dim3(256), 0, net->stream, (const uint32_t *)net->csr_t_edge, (const uint32_t *)net->csr_post,
+                           (const uint32_t *)net->csr_edge_slot, (const float *)net->csr_w, net->q0, span[0], found, index_d.get(), w_d.get());
+    HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+    HIP_TRY(copy_sync(net, index, index_d, (size_t)found * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    HIP_TRY(copy_sync(net, weights, w_d, (size_t)found * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    return SNN_OK;
+}
+
+int snn_graph_csr_incoming(snn_network_t *net, uint32_t post, uint32_t *pre_index, float *weights, uint64_t capacity, uint64_t *count) ABI_TRY
+{
+    TRY(graph_csr_begin(net));
+    if (!count) return fail(SNN_ERR_BAD_ARG, "count is null");
+    *count = 0;
+    if (post >= net->nn) return fail(SNN_ERR_BAD_ARG, "post " + std::to_string(post) + " is not below n_neurons = " + std::to_string(net->nn));
+    if (post < net->q0 || post >= net->q0 + net->n_loc)
+        return fail(SNN_ERR_BAD_ARG, "post " + std::to_string(post) + " is outside the columns this shard owns, [" + std::to_string(net->q0) +
+                                     ", " + std::to_string(net->q0 + net->n_loc) + ")");
+    return graph_csr_line(net, true, post - net->q0, pre_index, weights, capacity, count);
+}
+ABI_CATCH
+
+int snn_graph_csr_outgoing(snn_network_t *net, uint32_t pre, uint32_t *post_index, float *weights, uint64_t capacity, uint64_t *count) ABI_TRY
+{
+    TRY(graph_csr_begin(net));
+    if (!count) return fail(SNN_ERR_BAD_ARG, "count is null");
+    *count = 0;
+    if (pre >= net->n_tot) return fail(SNN_ERR_BAD_ARG, "pre " + std::to_string(pre) + " is not below n_tot = " + std::to_string(net->n_tot));
+    return graph_csr_line(net, false, pre, post_index, weights, capacity, count);
+}
+ABI_CATCH
+
 int snn_network_use_csr(snn_network_t *net, int enable) ABI_TRY
 {
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");

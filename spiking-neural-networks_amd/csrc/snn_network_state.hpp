@@ -26,6 +26,7 @@
 #include "snn_kernels_dense_step.hpp"
 #include "snn_kernels_exchange.hpp"
 #include "snn_kernels_graph_query.hpp"
+#include "snn_kernels_graph_query_csr.hpp"
 #include "snn_kernels_inputs.hpp"
 #include "snn_kernels_misc.hpp"
 #include "snn_kernels_resident.hpp"

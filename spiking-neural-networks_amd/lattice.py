@@ -757,6 +757,13 @@ class LatticeNetwork:
         self.lattices, self.spike_train_lattices = {}, {}
         self.connecting = {}              # (GraphPosition pre, GraphPosition post) -> weight
         self.connecting_nodes = []        # nodes of the connecting graph in insertion order (its matrix index)
+        # Opt-in (a sparse LatticeNetworkGPU sets it): connect(pre_id, post_id, ConnectionRule, WeightRule) between two lattices keeps
+        # the RECORD instead of one dict entry per edge.  One connect call rewrites its whole block (the pair loop of
+        # neuron/mod.rs:1845-1935), so the blocks are disjoint and each is either "dict" (its edges in `connecting`) or "record"
+        # (connecting_rules[(pre_id, post_id)] = (ConnectionRule, WeightRule); while a network on the device runs it, that handle's
+        # weights).  The readers treat a record block as a rule-held lattice is treated.
+        self.hold_connecting_rules = False
+        self.connecting_rules = {}
         self.electrical_synapse, self.chemical_synapse = True, False
         self.internal_clock = 0
         self.parallel = False
@@ -765,7 +772,19 @@ class LatticeNetwork:
 
     def clear(self):                                            # neuron/mod.rs:1681-1686
         self.lattices, self.spike_train_lattices = {}, {}
-        self.connecting, self.connecting_nodes = {}, []
+        self.connecting, self.connecting_nodes, self.connecting_rules = {}, [], {}
+
+    def __deepcopy__(self, memo):
+        """a copy carries the records; weights of a record block that live only on the device are brought home first"""
+        for key in list(self.connecting_rules):
+            g = self._live(key)
+            if g is not None and g._block_may_differ(key):
+                self._materialise_block(key)
+        new = type(self).__new__(type(self))
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            new.__dict__[k] = copy.deepcopy(v, memo)
+        return new
 
     @classmethod
     def generate_network(cls, lattices=(), spike_train_lattices=()):
@@ -809,7 +828,18 @@ class LatticeNetwork:
             return self.connect_internally(presynaptic_id, connection_conditional, weight_logic)
         pre = self.lattices.get(presynaptic_id) or self.spike_train_lattices[presynaptic_id]
         post = self.lattices[postsynaptic_id]
-        graph = _rule_graph(connection_conditional, weight_logic, (pre.rows, pre.cols), (post.rows, post.cols))
+        key = (presynaptic_id, postsynaptic_id)
+        records = _rule_records(connection_conditional, weight_logic)
+        if records is not None and self.hold_connecting_rules:
+            # the record IS the block: its dict entries go, both lattices' nodes join the connecting graph as _connect_graph adds them
+            if self.connecting:
+                for edge in [e for e in self.connecting if e[0].id == presynaptic_id and e[1].id == postsynaptic_id]:
+                    del self.connecting[edge]
+            self._add_block_nodes(presynaptic_id, pre, postsynaptic_id, post)
+            self.connecting_rules[key] = records
+            return None
+        self.connecting_rules.pop(key, None)                     # (a record held for this block: replaced by what follows)
+        graph = None if records is None else rule_pairs(*records, (pre.rows, pre.cols), (post.rows, post.cols))
         if graph is not None:
             return self._connect_graph(presynaptic_id, pre, postsynaptic_id, post, *graph)
         for a in ((r, c) for r in range(pre.rows) for c in range(pre.cols)):
@@ -824,16 +854,20 @@ class LatticeNetwork:
                 else:
                     self.connecting.pop(key, None)
 
-    def _connect_graph(self, presynaptic_id, pre, postsynaptic_id, post, on, w):
-        """the closure form's effect for a mask / weight matrix [n_pre, n_post]: the same nodes in the same order, the same edges"""
+    def _add_block_nodes(self, presynaptic_id, pre, postsynaptic_id, post):
+        """add_node for a whole block in the order the pair loop meets the nodes: the first pre, every post, then the other pres"""
         pre_nodes = [GraphPosition(presynaptic_id, (r, c)) for r in range(pre.rows) for c in range(pre.cols)]
         post_nodes = [GraphPosition(postsynaptic_id, (r, c)) for r in range(post.rows) for c in range(post.cols)]
         if pre_nodes and post_nodes:
-            # add_node in the order the pair loop meets them: the first pre, every post, then the other pres
             for node in [pre_nodes[0]] + post_nodes + pre_nodes[1:]:
                 if node not in self._node_set():
                     self.connecting_nodes.append(node)
                     self._nodes.add(node)
+        return pre_nodes, post_nodes
+
+    def _connect_graph(self, presynaptic_id, pre, postsynaptic_id, post, on, w):
+        """the closure form's effect for a mask / weight matrix [n_pre, n_post]: the same nodes in the same order, the same edges"""
+        pre_nodes, post_nodes = self._add_block_nodes(presynaptic_id, pre, postsynaptic_id, post)
         had = bool(self.connecting)
         for i, a in enumerate(pre_nodes):
             row_on, row_w = on[i], w[i]
@@ -877,8 +911,51 @@ class LatticeNetwork:
     def get_connecting_position_to_index(self):
         return self.connecting_position_to_index
 
+    # -- record blocks (hold_connecting_rules) ------------------------------------------------------------------------------
+    def _live(self, key):
+        """the network on the device that holds the weights of record block `key`, while its handle exists"""
+        post = self.lattices.get(key[1])
+        return post._live() if post is not None else None
+
+    def _record_pairs(self, key, pre_index, post_index):
+        """(connected bool, weights float32) [n_pre, n_post] of the pairs pre_index x post_index (lattice-local; None: every cell
+        of that side) of record block `key` -- from the device while a handle holds the weights (right under plasticity), else from
+        the record's twins on those rows / columns.  O(pairs asked for)."""
+        pre, post = self._any(key[0]), self.lattices[key[1]]
+        n_pre, n_post = pre.rows * pre.cols, post.rows * post.cols
+        g = self._live(key)
+        if g is None:
+            return rule_pairs(*self.connecting_rules[key], (pre.rows, pre.cols), (post.rows, post.cols), pre_index, post_index)
+        first_pre, first_post = g._dn.lattice_range(key[0])[0], g._dn.lattice_range(key[1])[0]
+        if pre_index is None and post_index is not None and len(post_index) == 1:             # one column
+            on, w = np.zeros((n_pre, 1), bool), np.zeros((n_pre, 1), np.float32)
+            index, weights = g._dn.graph_incoming(first_post + post_index[0])
+            mine = (index >= first_pre) & (index < first_pre + n_pre)
+            on[index[mine] - first_pre, 0], w[index[mine] - first_pre, 0] = True, weights[mine]
+            return on, w
+        if post_index is None and pre_index is not None and len(pre_index) == 1:             # one row
+            on, w = np.zeros((1, n_post), bool), np.zeros((1, n_post), np.float32)
+            index, weights = g._dn.graph_outgoing(first_pre + pre_index[0])
+            mine = (index >= first_post) & (index < first_post + n_post)
+            on[0, index[mine] - first_post], w[0, index[mine] - first_post] = True, weights[mine]
+            return on, w
+        rows = np.arange(n_pre) if pre_index is None else np.asarray(pre_index)
+        cols = np.arange(n_post) if post_index is None else np.asarray(post_index)
+        p, q = np.meshgrid(rows + first_pre, cols + first_post, indexing="ij")
+        w, on = g._dn.graph_lookup(p.reshape(-1), q.reshape(-1))
+        return on.reshape(p.shape), w.reshape(p.shape)
+
+    def _materialise_block(self, key):
+        """record block `key` becomes a dict block: its edges as the device holds them now (or as the record gives them) go into
+        `connecting`, as lattice.weights turns a rule-held lattice into matrices"""
+        on, w = self._record_pairs(key, None, None)
+        del self.connecting_rules[key]
+        self._connect_graph(key[0], self._any(key[0]), key[1], self.lattices[key[1]], on, w)
+
     def get_connecting_weights(self):
-        """the connecting graph's matrix, absent edges 0 (interface lattices/mod.rs:893-903)"""
+        """the connecting graph's matrix, absent edges 0 (interface lattices/mod.rs:893-903); a record block is materialised"""
+        for key in list(self.connecting_rules):
+            self._materialise_block(key)
         index = self.connecting_position_to_index
         m = np.zeros((len(index), len(index)), np.float32)
         for (pre, post), w in self.connecting.items():
@@ -897,6 +974,12 @@ class LatticeNetwork:
         nodes = self._node_set()
         if presynaptic not in nodes or postsynaptic not in nodes:
             raise KeyError("GraphError::PositionNotFound")
+        key = (presynaptic.id, postsynaptic.id)
+        if key in self.connecting_rules:
+            pre, post = self._any(key[0]), self.lattices[key[1]]
+            on, w = self._record_pairs(key, [presynaptic.pos[0] * pre.cols + presynaptic.pos[1]],
+                                       [postsynaptic.pos[0] * post.cols + postsynaptic.pos[1]])
+            return float(w[0, 0]) if on[0, 0] else 0.0
         return float(self.connecting.get((presynaptic, postsynaptic), 0.0))
 
     def get_incoming_connections_within_lattice(self, id, position):
@@ -910,14 +993,26 @@ class LatticeNetwork:
         gp = GraphPosition(id, position)
         if gp not in self._node_set():
             raise KeyError(f"Position {position} not found in lattice")
-        return {pre for (pre, post) in self.connecting if post == gp}
+        found = {pre for (pre, post) in self.connecting if post == gp}
+        for key in self.connecting_rules:
+            if key[1] == id:
+                cols = self._any(key[0]).cols
+                on, _ = self._record_pairs(key, None, [position[0] * self.lattices[id].cols + position[1]])
+                found |= {GraphPosition(key[0], (int(i) // cols, int(i) % cols)) for i in np.nonzero(on[:, 0])[0]}
+        return found
 
     def get_outgoing_connectings_across_lattices(self, id, position):
         self._lattice(id)
         gp = GraphPosition(id, position)
         if gp not in self._node_set():
             raise KeyError(f"Position {position} not found in lattice")
-        return {post for (pre, post) in self.connecting if pre == gp}
+        found = {post for (pre, post) in self.connecting if pre == gp}
+        for key in self.connecting_rules:
+            if key[0] == id:
+                cols = self.lattices[key[1]].cols
+                on, _ = self._record_pairs(key, [position[0] * self.lattices[id].cols + position[1]], None)
+                found |= {GraphPosition(key[1], (int(j) // cols, int(j) % cols)) for j in np.nonzero(on[0])[0]}
+        return found
 
     def get_neuron(self, id, row, col):
         return self._lattice(id).get_neuron(row, col)
@@ -1231,11 +1326,18 @@ class LatticeNetworkGPU:
     The host container (`self.network`, a LatticeNetwork) holds the network between runs: building methods (connect,
     add_lattice, set_neuron, apply_* ...) edit it and drop the device copy, the next run_lattices uploads again;
     everything that only reads (get_weight, get_neuron, connecting_weights ...) is answered from it -- every
-    run_lattices ends with the download of state, weights and histories."""
+    run_lattices ends with the download of state, weights and histories.
+
+    sparse=True: the handle holds a sparse (CSR) graph instead of the dense matrix -- what a network needs whose N x N matrix
+    cannot exist.  Rule-held lattices and record-connected blocks between lattices (LatticeNetwork.hold_connecting_rules, set on
+    the network this object holds) are merged on the device; what the sparse handle refuses surfaces as the library's error."""
     network_type = None        # host container class (LatticeNetwork unless a subclass says otherwise)
 
-    def __init__(self, network=None, device=0, graph_history_order=2):
+    def __init__(self, network=None, device=0, graph_history_order=2, sparse=False):
         object.__setattr__(self, "network", network if network is not None else (self.network_type or LatticeNetwork)())
+        self._sparse = bool(sparse)
+        if self._sparse:
+            self.network.hold_connecting_rules = True
         self._device = device
         self._dn = None
         self._graph_hist = {}
@@ -1247,12 +1349,12 @@ class LatticeNetworkGPU:
             self._ensure()                      # from_network converts right away, as the reference does
 
     @classmethod
-    def from_network(cls, network, device=0):                   # gpu_lattices/mod.rs:1636-1651
-        return cls(copy.deepcopy(network), device=device)
+    def from_network(cls, network, device=0, sparse=False):     # gpu_lattices/mod.rs:1636-1651
+        return cls(copy.deepcopy(network), device=device, sparse=sparse)
 
     @classmethod
-    def generate_network(cls, lattices=(), spike_train_lattices=(), device=0):   # interface lattices/mod.rs:1465-1500
-        g = cls(device=device)
+    def generate_network(cls, lattices=(), spike_train_lattices=(), device=0, sparse=False):   # interface lattices/mod.rs:1465-1500
+        g = cls(device=device, sparse=sparse)
         for l in lattices:
             g.add_lattice(l)
         for l in spike_train_lattices:
@@ -1313,7 +1415,11 @@ class LatticeNetworkGPU:
     def _dirty(self):
         if self._dn is not None:
             # the device copy goes: a rule-held lattice whose weights may no longer be its rule's brings them home first (a static
-            # one stays rule-held -- the rule recreates its weights bit for bit)
+            # one stays rule-held -- the rule recreates its weights bit for bit); a record block between lattices likewise
+            for key in list(self.network.connecting_rules):
+                post = self.network.lattices.get(key[1])
+                if post is not None and getattr(post, "_device", None) is self and self._block_may_differ(key):
+                    self.network._materialise_block(key)
             for l in self.network.lattices.values():
                 if getattr(l, "_device", None) is self:
                     if l.rule_held and self._may_differ(l):
@@ -1329,11 +1435,38 @@ class LatticeNetworkGPU:
         for it in a run since the upload"""
         return lattice.id in self._plastic
 
-    def _block(self, id):
-        """(weights float32[n, n], connections uint32[n, n]) of lattice `id` as the handle holds them now"""
+    def _block_may_differ(self, key):
+        """the same for record block (pre_id, post_id): a plastic lattice's rule moves the weights INTO its neurons and those OUT
+        of them, so a block may differ when either end ran with plasticity"""
+        return key[0] in self._plastic or key[1] in self._plastic
+
+    def _csr_edges(self):
+        """(pre int64[nnz], post int64[nnz]) of a sparse handle's stored edges, in the edge order of get_graph_csr"""
+        rp, pi = self._dn.graph_csr_structure()
+        return pi.astype(np.int64), np.repeat(self._dn.owned, np.diff(rp.astype(np.int64)))
+
+    def _block(self, id, edges=None):
+        """(weights float32[n, n], connections uint32[n, n]) of lattice `id` as the handle holds them now; `edges`: what
+        _csr_edges and get_graph_csr returned, when the caller already has them (sparse handles)"""
         first, count = self._dn.lattice_range(id)
+        if self._sparse:
+            pre, post, values = edges if edges is not None else (*self._csr_edges(), self._dn.get_graph_csr())
+            mine = (pre >= first) & (pre < first + count) & (post >= first) & (post < first + count)
+            w, c = np.zeros((count, count), np.float32), np.zeros((count, count), np.uint32)
+            w[pre[mine] - first, post[mine] - first] = values[mine]
+            c[pre[mine] - first, post[mine] - first] = 1
+            return w, c
         w, c = self._dn.get_graph_rows(first, count)
         return w[:, first:first + count].copy(), c[:, first:first + count].copy()
+
+    def _block_values(self, id, values, edges):
+        """a per-edge array of a sparse handle (traces) as lattice `id`'s [n, n] block"""
+        first, count = self._dn.lattice_range(id)
+        pre, post = edges[0], edges[1]
+        mine = (pre >= first) & (pre < first + count) & (post >= first) & (post < first + count)
+        out = np.zeros((count, count), values.dtype)
+        out[pre[mine] - first, post[mine] - first] = values[mine]
+        return out
 
     def _note_plasticity(self):
         self._plastic |= {id for id, l in self.network.lattices.items() if l.do_plasticity}
@@ -1362,7 +1495,7 @@ class LatticeNetworkGPU:
             self._dn.add_lattice(id, l.rows, l.cols)
         for id, l in network.spike_train_lattices.items():
             self._dn.add_spike_train_lattice(id, l.rows, l.cols)
-        self._dn.finalize()
+        self._dn.finalize(csr=self._sparse)
         self._upload()
         return self._dn
 
@@ -1381,6 +1514,8 @@ class LatticeNetworkGPU:
         nn, nt = dn.n_neurons, dn.n_tot
         if nn == 0 or nt == 0:
             return
+        if self._sparse:
+            return self._upload_sparse()
         # A freshly finalized dense handle holds no edge.  A materialised lattice uploads its own rows (its block, every other
         # column absent); a rule-held one is one connect_by_rule on the device and a lattice that was never connected leaves its
         # block empty; the connecting graph's edges go up last, in one edit.  Nothing of size N^2 exists on the host unless a
@@ -1398,6 +1533,8 @@ class LatticeNetworkGPU:
         for id, l in net.lattices.items():
             if l.rule_held and l._rule is not None:
                 dn.connect_by_rule(id, id, *l._rule)
+        for (pre_id, post_id), records in net.connecting_rules.items():      # record blocks between lattices: no dict entry per edge
+            dn.connect_by_rule(pre_id, post_id, *records)
         if net.connecting:
             keys = list(net.connecting)
             dn.graph_edit([self._global(a) for a, _ in keys], [self._global(b) for _, b in keys],
@@ -1411,11 +1548,59 @@ class LatticeNetworkGPU:
                 t = np.zeros((count, nn), np.float32)
                 t[:, first:first + count] = l.traces
                 dn.set_trace_rows(first, t)
+        self._upload_clocks()
+
+    def _upload_clocks(self):
         # internal_clock: lattice_network.internal_clock (gpu_lattices/mod.rs:1630): a network that has already run goes on at its
         # clock (last_firing_time values are absolute step numbers); every spike-train lattice keeps its own
+        dn, net = self._dn, self.network
         dn.set_clock(int(getattr(net, "internal_clock", 0) or 0))
         for id, l in net.spike_train_lattices.items():
             dn.set_spike_train_clock(id, int(getattr(l, "internal_clock", 0) or 0))
+
+    def _upload_sparse(self):
+        """the graph of a sparse handle.  (1) What the host holds edge by edge -- materialised lattices, the connecting dict -- is
+        assembled into host CSR (rows = the neurons in ascending order) and set once: O(those edges).  (2) Every rule-held
+        lattice's record and every record block go up in ONE connect_sparse, merged on the device: the blocks are disjoint, so
+        the merge keeps the edges of (1).  With nothing materialised (1) is skipped and nothing of size N^2 or nnz exists here."""
+        dn, net = self._dn, self.network
+        nn = dn.n_neurons
+        pre, post, weights = [], [], []
+        for id, l in net.lattices.items():
+            l._device = self
+            first, count = dn.lattice_range(id)
+            if not l.rule_held and count:
+                i, j = np.nonzero(l.connections)
+                pre.append(i.astype(np.int64) + first)
+                post.append(j.astype(np.int64) + first)
+                weights.append(np.asarray(l.weights, np.float32)[i, j])
+        if net.connecting:
+            keys = list(net.connecting)
+            pre.append(np.array([self._global(a) for a, _ in keys], np.int64))
+            post.append(np.array([self._global(b) for _, b in keys], np.int64))
+            weights.append(np.array([net.connecting[k] for k in keys], np.float32))
+        if pre:
+            pre, post, weights = np.concatenate(pre), np.concatenate(post), np.concatenate(weights)
+            order = np.lexsort((pre, post))                          # row by row, ascending presynaptic index inside a row
+            row_ptr = np.concatenate([[0], np.cumsum(np.bincount(post, minlength=nn))]).astype(np.uint64)
+            dn.set_graph_csr(row_ptr, pre[order].astype(np.uint32), weights[order])
+        plan = [(id, id, *l._rule) for id, l in net.lattices.items() if l.rule_held and l._rule is not None]
+        plan += [(pre_id, post_id, *records) for (pre_id, post_id), records in net.connecting_rules.items()]
+        if plan:
+            dn.connect_sparse(plan)
+        modulated = [(id, l) for id, l in net.lattices.items() if isinstance(l, RewardModulatedLattice)]
+        for id, l in modulated:
+            m = l.reward_modulator
+            dn.set_reward_modulator(id, m.dopamine, m.tau_d, m.tau_c, m.a_plus, m.a_minus, m.tau_plus, m.tau_minus, m.dt, l.do_modulation)
+        if modulated:
+            edges = self._csr_edges()
+            traces = np.zeros(edges[0].size, np.float32)
+            for id, l in modulated:
+                first, count = dn.lattice_range(id)
+                mine = (edges[0] >= first) & (edges[0] < first + count) & (edges[1] >= first) & (edges[1] < first + count)
+                traces[mine] = np.asarray(l.traces, np.float32)[edges[0][mine] - first, edges[1][mine] - first]
+            dn.set_traces_csr(traces)
+        self._upload_clocks()
 
     def _global(self, gp):
         first, _ = self._dn.lattice_range(gp.id)
@@ -1460,14 +1645,18 @@ class LatticeNetworkGPU:
         net.internal_clock = dn.clock
         nn, nt = dn.n_neurons, dn.n_tot
         have_graph = bool(nn and nt)
+        edges = None                                            # a sparse handle's edges, fetched once if a lattice needs them
         for id, l in net.lattices.items():
             _download_neurons(dn, id, _flat(l))
             l.internal_clock = net.internal_clock
             if have_graph and not l.rule_held:                  # (a rule-held lattice's weights stay on the device: asked there)
                 first, count = dn.lattice_range(id)
-                l.weights, l.connections = self._block(id)
+                if self._sparse and edges is None:
+                    edges = (*self._csr_edges(), dn.get_graph_csr())
+                l.weights, l.connections = self._block(id, edges)
                 if isinstance(l, RewardModulatedLattice):
-                    l.traces = dn.get_trace_rows(first, count)[:, first:first + count].copy()
+                    l.traces = (self._block_values(id, dn.get_traces_csr(), edges) if self._sparse
+                                else dn.get_trace_rows(first, count)[:, first:first + count].copy())
                     l.reward_modulator.dopamine = float(dn.dopamine(id))
         for id, l in net.spike_train_lattices.items():
             l.internal_clock = dn.spike_train_clock(id)             # SpikeTrainLattice::internal_clock, neuron/mod.rs:1318
@@ -1534,21 +1723,22 @@ class LatticeGPU:
     """LatticeGPU (backend/src/neuron/gpu_lattices/mod.rs:327-1118): a network of one lattice."""
     lattice_type = Lattice
 
-    def __init__(self, id=0, device=0):
+    def __init__(self, id=0, device=0, sparse=False):
         self._lattice = self.lattice_type(id)
         self._device = device
+        self._sparse = bool(sparse)                                 # the handle holds a sparse (CSR) graph
         self._net = None
 
     @classmethod
-    def from_lattice(cls, lattice, device=0):                   # gpu_lattices/mod.rs:496-511
-        g = cls(lattice.id, device=device)
+    def from_lattice(cls, lattice, device=0, sparse=False):     # gpu_lattices/mod.rs:496-511
+        g = cls(lattice.id, device=device, sparse=sparse)
         g._lattice = copy.deepcopy(lattice)
         return g
 
     def _ensure(self):
         if self._net is None:
             host = LatticeNetwork.generate_network([self._lattice])
-            self._net = LatticeNetworkGPU(host, device=self._device, graph_history_order=1)
+            self._net = LatticeNetworkGPU(host, device=self._device, graph_history_order=1, sparse=self._sparse)
         return self._net
 
     def _dirty(self):

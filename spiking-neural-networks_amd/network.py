@@ -397,7 +397,11 @@ class DeviceNetwork:
                                               c.ctypes.data_as(_lib.u32p)))
         return w, c
 
-    # the Graph trait on the device matrix (graph/mod.rs:42-72); interleaved global indices, dense handles
+    # the Graph trait on the device graph (graph/mod.rs:42-72); interleaved global indices.  A dense handle is asked through
+    # snn_graph_*, a sparse one (finalize(csr=True)) through snn_graph_csr_*: the same answers, and a structure that is fixed
+    def _graph_fn(self, name):
+        return getattr(self._L, ("snn_graph_csr_" if getattr(self, "csr", False) else "snn_graph_") + name)
+
     @staticmethod
     def _pairs(pre, post):
         p = np.ascontiguousarray(np.asarray(pre).reshape(-1), dtype=np.uint32)
@@ -412,13 +416,16 @@ class DeviceNetwork:
         """lookup_weight for the pairs (pre[k], post[k]): (weights float32[n], connected bool[n]); an absent edge reads 0.0 / False"""
         p, q = self._pairs(pre, post)
         w, c = _out(p.size, np.float32), _out(p.size, np.uint8)
-        self._check(self._L.snn_graph_lookup(self._h, p.ctypes.data_as(_lib.u32p), q.ctypes.data_as(_lib.u32p), p.size,
-                                            w.ctypes.data_as(_lib.f32p), c.ctypes.data_as(_lib.u8p)))
+        self._check(self._graph_fn("lookup")(self._h, p.ctypes.data_as(_lib.u32p), q.ctypes.data_as(_lib.u32p), p.size,
+                                               w.ctypes.data_as(_lib.f32p), c.ctypes.data_as(_lib.u8p)))
         return w, c != 0
 
     def graph_edit(self, pre, post, weights, connected=None):
         """edit_weight for the pairs (pre[k], post[k]): Some(weights[k]) where connected[k] (None: everywhere), None elsewhere.  Applied
-        as if one after another: of a pair listed twice the last wins.  A NaN weight of a connected pair is refused."""
+        as if one after another: of a pair listed twice the last wins.  A NaN weight of a connected pair is refused.
+        On a sparse handle the structure is fixed: connected[k] on a stored edge sets its weight and not connected[k] on an absent
+        pair is a no-op; connecting an absent pair or disconnecting a stored edge is refused (SnnError, BAD_ARG, the pair named)
+        before anything is written -- connect_sparse / set_graph_csr are what changes a structure."""
         p, q = self._pairs(pre, post)
         w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
         if np.ndim(weights) == 0:                # one weight for every pair
@@ -426,8 +433,8 @@ class DeviceNetwork:
         c = np.ones(p.size, np.uint8) if connected is None else np.ascontiguousarray(np.asarray(connected).reshape(-1) != 0, dtype=np.uint8)
         if w.size != p.size or c.size != p.size:
             raise ValueError("weights / connected must have one entry per pair")
-        self._check(self._L.snn_graph_edit(self._h, p.ctypes.data_as(_lib.u32p), q.ctypes.data_as(_lib.u32p),
-                                          w.ctypes.data_as(_lib.f32p), c.ctypes.data_as(_lib.u8p), p.size))
+        self._check(self._graph_fn("edit")(self._h, p.ctypes.data_as(_lib.u32p), q.ctypes.data_as(_lib.u32p),
+                                           w.ctypes.data_as(_lib.f32p), c.ctypes.data_as(_lib.u8p), p.size))
 
     def _graph_line(self, fn, which):
         n = C.c_uint64()
@@ -440,13 +447,14 @@ class DeviceNetwork:
         return index, w
 
     def graph_incoming(self, post):
-        """get_incoming_connections: (pre index uint32[count] ascending, weights float32[count]) of the edges into `post`"""
-        return self._graph_line(self._L.snn_graph_incoming, int(post))
+        """get_incoming_connections: (pre index uint32[count] ascending, weights float32[count]) of the edges into `post`; dense
+        and sparse handles alike"""
+        return self._graph_line(self._graph_fn("incoming"), int(post))
 
     def graph_outgoing(self, pre):
         """get_outgoing_connections: (post index uint32[count] ascending, weights float32[count]) of the edges out of `pre` (a shard
-        handle: into the columns it owns)"""
-        return self._graph_line(self._L.snn_graph_outgoing, int(pre))
+        handle: into the columns it owns); dense and sparse handles alike"""
+        return self._graph_line(self._graph_fn("outgoing"), int(pre))
 
     def set_graph_csr(self, row_ptr, pre_index, weights):
         """CSR by OWNED postsynaptic neuron in ascending global order (self.owned): row_ptr[n_owned + 1], pre_index
