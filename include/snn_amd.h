@@ -258,7 +258,8 @@ int snn_get_graph_csr_structure(snn_network_t *net, uint64_t *row_ptr, uint32_t 
  * written and snn_last_error names the first offending pair by its position in the call; n == 0 is SNN_OK and touches nothing;
  * null pointers with n > 0 are SNN_ERR_BAD_ARG; deferred plasticity updates are applied first, so the four agree bit for bit
  * with snn_get_graph_csr at that moment.
- * What differs: the STRUCTURE IS FIXED, so snn_graph_csr_edit edits the weights of stored edges only.  connected[k] != 0 on a
+ * What differs: for snn_graph_csr_edit the STRUCTURE IS FIXED (snn_graph_csr_edit_structure, below, is the call that connects and
+ * removes), so it edits the weights of stored edges only.  connected[k] != 0 on a
  * stored edge sets its weight; connected[k] == 0 on an absent pair is a no-op; connected[k] != 0 on an absent pair and
  * connected[k] == 0 on a stored edge are SNN_ERR_BAD_ARG (the message names the pair; snn_connect_by_rules_csr /
  * snn_set_graph_csr are what changes a structure) -- every occurrence of a pair is held to this, found in one resolve pass over
@@ -275,6 +276,31 @@ int snn_graph_csr_edit(snn_network_t *net, const uint32_t *pre, const uint32_t *
                        size_t n);
 int snn_graph_csr_incoming(snn_network_t *net, uint32_t post, uint32_t *pre_index, float *weights, uint64_t capacity, uint64_t *count);
 int snn_graph_csr_outgoing(snn_network_t *net, uint32_t pre, uint32_t *post_index, float *weights, uint64_t capacity, uint64_t *count);
+
+/* edit_weight(pre, post, Option<f32>) on a SPARSE handle WITH the structure (graph/mod.rs:42-72, 204-213): the argument contract of
+ * snn_graph_edit on a dense handle.  connected[k] != 0 is Some(weights[k]) whether or not the pair is stored -- an absent pair is
+ * CONNECTED, a stored edge gets the weight, Some(0.0f) is an edge; connected[k] == 0 is None whether or not the pair is stored -- a
+ * stored edge is REMOVED (its row is one entry shorter, which the averager sees), an absent pair stays absent.  The edits apply as
+ * if one after another: of a pair listed more than once the last occurrence wins (connect-then-remove leaves it absent,
+ * remove-then-connect leaves it present with the last weight).  snn_graph_csr_edit above stays what it is: the call that refuses
+ * to change a structure.
+ * Every pair is checked before anything is written -- pre < n_tot, post < n_neurons and inside the columns a shard owns, no NaN
+ * on a connected pair -- with the codes and the "pair k (pre .., post ..)" naming of snn_graph_csr_edit.  n == 0 is SNN_OK; null
+ * pointers with n > 0 are SNN_ERR_BAD_ARG.  A handle that holds no graph yet holds the empty one: connects build a graph from it.
+ * The list is sorted by (post, pre) on the host and merged into the stored rows ON THE DEVICE, one wavefront per row, after
+ * deferred plasticity updates were applied: O(stored entries + edits * log), nothing of size N^2.  Kept edges keep the weight
+ * they have on the device NOW and, on a handle with reward modulation or connection kinds, their trace / dw / counter, bit for
+ * bit; inserted and reweighted edges start those at 0; removed edges are gone.  When no pair inserts or removes, the call IS
+ * snn_graph_csr_edit (in place, no rebuild).  Otherwise the merged graph is downloaded once (12 bytes per edge + 4 per row) and
+ * committed as by snn_set_graph_csr -- SELL-64, transpose, gather plan, step image, halo and cell lists of a contiguous shard are
+ * rebuilt on the host -- and the edge order of snn_get_graph_csr and the _csr trace forms is row by row in ascending presynaptic
+ * index (snn_get_graph_csr_structure returns it; snn_graph_csr_nnz the new count).
+ * All or nothing: a refusal, an allocation that fails or a total of 2^32-1 stored edges or more (SNN_ERR_DIM_MISMATCH) leave
+ * structure, weights and per-edge state as they were (the one exception is snn_set_graph_csr's: planes allocated after the
+ * commit).  SNN_ERR_BAD_STATE: a dense handle (snn_graph_edit is structural already), a handle that is not finalized, a shard by
+ * lattice (range-set ownership: not covered). */
+int snn_graph_csr_edit_structure(snn_network_t *net, const uint32_t *pre, const uint32_t *post, const float *weights,
+                                 const uint8_t *connected, size_t n);
 
 /* Connect by rule on SPARSE handles: the CSR graph is built on the device.  A record holds the arguments of snn_connect_by_rule
  * after the handle, with the same meaning, validation and per-pair formulas (pair index, predicate, draw, weight).  The records

@@ -216,6 +216,7 @@ SIGNATURES = {
     "snn_get_graph_csr_structure": (C.c_int, [H, u64p, u32p, C.c_uint64]),
     "snn_graph_csr_lookup": (C.c_int, [H, u32p, u32p, C.c_size_t, f32p, u8p]),
     "snn_graph_csr_edit": (C.c_int, [H, u32p, u32p, f32p, u8p, C.c_size_t]),
+    "snn_graph_csr_edit_structure": (C.c_int, [H, u32p, u32p, f32p, u8p, C.c_size_t]),
     "snn_graph_csr_incoming": (C.c_int, [H, C.c_uint32, u32p, f32p, C.c_uint64, u64p]),
     "snn_graph_csr_outgoing": (C.c_int, [H, C.c_uint32, u32p, f32p, C.c_uint64, u64p]),
     "snn_connect_by_rules_csr": (C.c_int, [H, C.POINTER(ConnectRecord), C.c_uint32]),

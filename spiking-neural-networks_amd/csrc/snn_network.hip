@@ -850,8 +850,12 @@ namespace { int ensure_traces(snn_network *net); int ensure_pending(snn_network 
 // All or nothing: a failed call leaves the previous graph in place, intact -- except that the traces / dw / counters of a handle
 // with modulation or connection kinds are sized by the new graph and allocated after the commit: if THAT fails, the handle holds
 // the new graph without them.  Device memory peaks at old graph + new graph while the call runs.
+// `keep` (may be null): at the commit the planes of the replaced edges move there instead of being freed -- a structural edit
+// carries them over to the edges it keeps (snn_graph_csr_edit_structure).  Untouched when the call fails before the commit.
+struct CsrEdgePlanes { dev_ptr<float> trace, pending, edge_counter; };
+
 static int set_graph_csr_impl(snn_network_t *net, const uint64_t *row_ptr, const uint32_t *pre_index, const float *weights,
-                              uint64_t nnz)
+                              uint64_t nnz, CsrEdgePlanes *keep = nullptr)
 {
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
     if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
@@ -967,6 +971,7 @@ static int set_graph_csr_impl(snn_network_t *net, const uint64_t *row_ptr, const
     net->csr_img_hdr = std::move(img_hdr_d); net->csr_plan_win = std::move(plan_win_d); net->csr_img_rec = std::move(img_rec_d);
     net->img_records = img_records; net->img_staged_slices = img_staged_slices;
     net->img_stale = net->img_stale_direct = true;
+    if (keep) { keep->trace = std::move(net->trace); keep->pending = std::move(net->pending); keep->edge_counter = std::move(net->edge_counter); }
     net->trace = nullptr;                                        // traces belong to the replaced edges
     net->pending = nullptr; net->edge_counter = nullptr;         // ... and so do dw and the counters of its connections
     net->cross_checked = false;
@@ -1194,6 +1199,174 @@ ABI_CATCH
 int snn_connect_by_specs_csr(snn_network_t *net, const snn_connect_spec *specs, uint32_t n_specs) ABI_TRY
 {
     return connect_csr(net, nullptr, specs, n_specs);
+}
+ABI_CATCH
+
+// edit_weight(pre, post, Option<f32>) on a sparse handle, structure included (graph/mod.rs:42-72, 204-213): the sorted edit list
+// merged into the stored rows on the device (snn_kernels_graph_merge_csr.hpp), committed as connect_csr commits.  Nothing of the
+// handle is written before the commit -- or, when no pair inserts or removes, before the in-place store of snn_graph_csr_edit.
+int snn_graph_csr_edit_structure(snn_network_t *net, const uint32_t *pre, const uint32_t *post, const float *weights,
+                                 const uint8_t *connected, size_t n) ABI_TRY
+{
+    TRY(graph_csr_begin(net));
+    if (n == 0) return SNN_OK;
+    if (!pre || !post || !weights || !connected) return fail(SNN_ERR_BAD_ARG, "null pointer with n > 0");
+    // every pair is checked before anything is written: a refused call leaves the graph as it was
+    for (size_t k = 0; k < n; ++k) {
+        if (pre[k] >= net->n_tot || post[k] - net->q0 >= net->n_loc) return graph_pair_check(net, "pair " + std::to_string(k), pre[k], post[k]);
+        if (connected[k] && weights[k] != weights[k])
+            return fail(SNN_ERR_BAD_ARG, graph_csr_pair(k, pre[k], post[k]) + ": a connected edge carries a NaN weight; NaN is the absent-edge "
+                                         "sentinel of the dense form, which the sparse form refuses alike (graph/mod.rs:204-213).  Nothing of "
+                                         "this call was applied");
+    }
+    // "as if one after another": of a pair listed more than once the last occurrence decides, whatever the earlier ones asked for;
+    // the list sorted by (post, pre) is the order the rows of the merge read it in
+    hvec<uint64_t> order;
+    const size_t kept = graph_merge_order(pre, post, n, order);
+    if (kept >= 0xFFFFFFFFull) return fail(SNN_ERR_DIM_MISMATCH, "more than 2^32-2 distinct pairs in one call");
+    const uint32_t m = (uint32_t)kept, rows = net->n_loc;
+    const size_t hop = std::min(kept, GRAPH_PAIRS_HOP);
+    hvec<uint32_t> pre_h(hop), post_h(hop);
+    hvec<float> value_h(hop);
+    hvec<uint8_t> on_h(hop);
+    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
+    TRY(end_run(net));                     // a deferred update belongs to the weights the merge is about to read
+    const bool timing = getenv("SNN_DEBUG_EDIT_TIMING") != nullptr;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(now() - t).count(); };
+    const auto t_begin = now();
+    const uint32_t scan_edits = (m + 255u) / 256u, scan_rows = (rows + 255u) / 256u;
+    dev_ptr<uint32_t> pre_d, post_d, slot_d, ins_d, rem_d, len_d, ptr_d, new_pre_d, src_d;
+    dev_ptr<uint8_t> on_d;
+    dev_ptr<float> value_d, new_w_d;
+    dev_ptr<unsigned long long> sums_d;              // [blocks] block sums of a scan, then [1] its total
+    auto sized = [&](auto *dst, size_t bytes) -> int {
+        HIP_TRY(snn_malloc(dst, std::max<size_t>(bytes, 256)), SNN_ERR_BUFFER_CREATE);
+        return SNN_OK;
+    };
+    TRY(sized(&pre_d, kept * 4));
+    TRY(sized(&post_d, kept * 4));
+    TRY(sized(&value_d, kept * 4));
+    TRY(sized(&on_d, kept));
+    TRY(sized(&slot_d, kept * 4));
+    TRY(sized(&ins_d, (kept + 1) * 4));
+    TRY(sized(&rem_d, (kept + 1) * 4));
+    TRY(sized(&sums_d, ((size_t)std::max(scan_edits, scan_rows) + 1) * 8));
+    if (net->opt.pinned_copies && !net->copy_stage)           // (the staging buffer of copy_sync: allocated before the first write)
+        HIP_TRY(host_malloc(&net->copy_stage, (size_t)8 << 20, hipHostMallocDefault), SNN_ERR_BUFFER_CREATE);
+    // ---- the resolve pass: read only.  The sorted list goes up in hops; every pair finds its entry ----
+    for (size_t k = 0; k < kept; k += hop) {
+        const uint32_t h = (uint32_t)std::min(hop, kept - k);
+        for (uint32_t j = 0; j < h; ++j) {
+            const size_t src = (size_t)order[k + j];
+            pre_h[j] = pre[src]; post_h[j] = post[src]; value_h[j] = weights[src]; on_h[j] = connected[src] ? 1 : 0;
+        }
+        HIP_TRY(copy_sync(net, pre_d.get() + k, pre_h.data(), (size_t)h * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        HIP_TRY(copy_sync(net, post_d.get() + k, post_h.data(), (size_t)h * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        HIP_TRY(copy_sync(net, value_d.get() + k, value_h.data(), (size_t)h * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        HIP_TRY(copy_sync(net, on_d.get() + k, on_h.data(), h, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+        if (net->csr_ptr)
+            hipLaunchKernelGGL(k_graph_csr_find, dim3((h + 255u) / 256u), dim3(256), 0, net->stream, (const uint32_t *)net->csr_ptr,
+                               (const uint32_t *)net->csr_pre, (const float *)net->csr_w, (const uint32_t *)net->csr_row_len, net->q0,
+                               (const uint32_t *)(pre_d.get() + k), (const uint32_t *)(post_d.get() + k), h, slot_d.get() + k, (float *)nullptr,
+                               (uint8_t *)nullptr, (const uint8_t *)nullptr, 0ull, (unsigned long long *)nullptr);
+        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+    }
+    if (!net->csr_ptr)                     // no graph set yet: the empty one, no pair has an entry (GRAPH_CSR_NONE is all ones)
+        HIP_TRY(hipMemsetAsync(slot_d, 0xFF, kept * 4, net->stream), SNN_ERR_BUFFER_WRITE);
+    hipLaunchKernelGGL(k_graph_merge_flags, dim3(scan_edits), dim3(256), 0, net->stream, (const uint32_t *)slot_d, (const uint8_t *)on_d, m,
+                       ins_d.get(), rem_d.get());
+    HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+    // flags or lengths -> count + 1 offsets, in place (every thread reads its word before the block's first write), the total read back
+    auto scan = [&](uint32_t *words, uint32_t count, uint64_t *total) -> int {
+        const uint32_t blocks = (count + 255u) / 256u;
+        unsigned long long *total_d = sums_d.get() + blocks;
+        hipLaunchKernelGGL(k_connect_scan_local, dim3(blocks), dim3(256), 0, net->stream, (const uint32_t *)words, count, words, sums_d.get());
+        hipLaunchKernelGGL(k_connect_scan_sums, dim3(1), dim3(256), 0, net->stream, sums_d.get(), blocks, total_d);
+        hipLaunchKernelGGL(k_connect_scan_add, dim3(blocks), dim3(256), 0, net->stream, words, count, (const unsigned long long *)sums_d.get(),
+                           (const unsigned long long *)total_d);
+        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+        unsigned long long t = 0;
+        HIP_TRY(copy_sync(net, &t, total_d, 8, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+        *total = t;
+        return SNN_OK;
+    };
+    uint64_t inserts = 0, removes = 0;
+    TRY(scan(ins_d, m, &inserts));
+    TRY(scan(rem_d, m, &removes));
+    if (inserts == 0 && removes == 0) {
+        // ---- nothing inserts, nothing removes: the write pass of snn_graph_csr_edit, in place ("stay absent" has no entry and is
+        // skipped; no pair is listed twice) ----
+        if (!net->csr_ptr) return SNN_OK;
+        net->cross_checked = false;
+        net->img_stale = net->img_stale_direct = true;             // the step image's records are packed again before the next image step
+        hipLaunchKernelGGL(k_graph_csr_store, dim3(scan_edits), dim3(256), 0, net->stream, net->csr_w.get(), net->trace.get(),
+                           net->pending.get(), net->edge_counter.get(), (const uint32_t *)slot_d, (const unsigned long long *)nullptr,
+                           (const float *)value_d, m);
+        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+        HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
+        return SNN_OK;
+    }
+    // ---- the structural path: lengths, offsets, the 2^32-2 check, then every entry placed on its own ----
+    TRY(sized(&len_d, ((size_t)rows + 1) * 4));
+    GraphMergeArgs a{};
+    if (net->csr_ptr) { a.slice_ptr = net->csr_ptr; a.sell_pre = net->csr_pre; a.row_len = net->csr_row_len; a.sell_w = net->csr_w; }
+    a.edit_pre = pre_d; a.edit_post = post_d; a.ins_before = ins_d; a.rem_before = rem_d; a.edit_w = value_d;
+    a.n_edits = m; a.n_rows = rows; a.q0 = net->q0;
+    a.new_len = len_d;
+    hipLaunchKernelGGL(k_graph_merge_count, dim3(scan_rows), dim3(256), 0, net->stream, a);
+    HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+    uint64_t nnz = 0;
+    TRY(scan(len_d, rows, &nnz));
+    if (nnz >= 0xFFFFFFFFull)
+        return fail(SNN_ERR_DIM_MISMATCH, "the graph would hold " + std::to_string(nnz) + " stored synapses, more than 2^32-2 per handle");
+    if (nnz != net->nnz + inserts - removes) return fail(SNN_ERR_BAD_STATE, "the merged row lengths do not add up to stored + inserted - removed");
+    TRY(sized(&new_pre_d, nnz * 4));
+    TRY(sized(&new_w_d, nnz * 4));
+    TRY(sized(&src_d, nnz * 4));
+    a.new_ptr = len_d; a.new_pre = new_pre_d; a.new_w = new_w_d; a.new_src = src_d;
+    hipLaunchKernelGGL(k_graph_merge_fill, dim3(std::min<uint32_t>((rows + 3u) / 4u, 16384u)), dim3(256), 0, net->stream, a);
+    HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+    HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
+    const double ms_merge = ms_since(t_begin);
+    // ---- one download, then the host builder of snn_set_graph_csr: all or nothing from here as before here ----
+    const auto t_download = now();
+    hvec<uint32_t> ptr32((size_t)rows + 1), new_pre_h((size_t)nnz);
+    hvec<float> new_w_h((size_t)nnz);
+    HIP_TRY(copy_sync(net, ptr32.data(), len_d, ptr32.size() * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    if (nnz) {
+        HIP_TRY(copy_sync(net, new_pre_h.data(), new_pre_d, nnz * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+        HIP_TRY(copy_sync(net, new_w_h.data(), new_w_d, nnz * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    }
+    // (the commit peaks at old graph + new graph: everything but the source of every new edge goes now)
+    pre_d.reset(); post_d.reset(); value_d.reset(); on_d.reset(); slot_d.reset(); ins_d.reset(); rem_d.reset(); len_d.reset();
+    new_pre_d.reset(); new_w_d.reset(); sums_d.reset();
+    hvec<uint64_t> ptr64(ptr32.begin(), ptr32.end());
+    hvec<uint32_t>().swap(ptr32);
+    const double ms_download = ms_since(t_download);
+    const auto t_commit = now();
+    uint32_t no_pre = 0;
+    float no_w = 0.0f;
+    CsrEdgePlanes old;
+    TRY(set_graph_csr_impl(net, ptr64.data(), nnz ? new_pre_h.data() : &no_pre, nnz ? new_w_h.data() : &no_w, nnz, &old));
+    const double ms_commit = ms_since(t_commit);
+    // ---- per-edge state: the planes the handle carried, from the old entry of every kept edge to its new one (a handle with
+    // modulation or connection kinds has zeroed planes again by now; planes set without either are allocated here) ----
+    if (old.trace) TRY(ensure_traces(net));
+    if (old.pending) TRY(ensure_pending(net));
+    if (nnz && (old.trace || old.pending)) {
+        hipLaunchKernelGGL(k_graph_merge_carry, dim3(((uint32_t)nnz + 255u) / 256u), dim3(256), 0, net->stream, (const uint32_t *)src_d,
+                           (const uint32_t *)net->csr_edge_slot, (uint32_t)nnz, (const float *)old.trace, old.trace ? net->trace.get() : nullptr,
+                           (const float *)old.pending, old.pending ? net->pending.get() : nullptr, (const float *)old.edge_counter,
+                           old.edge_counter ? net->edge_counter.get() : nullptr);
+        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+        HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
+    }
+    if (timing)
+        fprintf(stderr, "[snn] edit_structure: %u edits (%llu inserts, %llu removes), %llu edges: resolve+merge %.3f ms, download %.3f ms, "
+                        "host builder %.3f ms, carry %.3f ms\n", m, (unsigned long long)inserts, (unsigned long long)removes,
+                (unsigned long long)nnz, ms_merge, ms_download, ms_commit, ms_since(t_commit) - ms_commit);
+    return SNN_OK;
 }
 ABI_CATCH
 

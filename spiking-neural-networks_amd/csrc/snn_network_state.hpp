@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -25,6 +26,7 @@
 #include "snn_kernels_csr.hpp"
 #include "snn_kernels_dense_step.hpp"
 #include "snn_kernels_exchange.hpp"
+#include "snn_kernels_graph_merge_csr.hpp"
 #include "snn_kernels_graph_query.hpp"
 #include "snn_kernels_graph_query_csr.hpp"
 #include "snn_kernels_inputs.hpp"

@@ -399,6 +399,7 @@ class DeviceNetwork:
 
     # the Graph trait on the device graph (graph/mod.rs:42-72); interleaved global indices.  A dense handle is asked through
     # snn_graph_*, a sparse one (finalize(csr=True)) through snn_graph_csr_*: the same answers, and a structure that is fixed
+    # unless graph_edit is asked to change it (structure=True: snn_graph_csr_edit_structure)
     def _graph_fn(self, name):
         return getattr(self._L, ("snn_graph_csr_" if getattr(self, "csr", False) else "snn_graph_") + name)
 
@@ -420,12 +421,15 @@ class DeviceNetwork:
                                                w.ctypes.data_as(_lib.f32p), c.ctypes.data_as(_lib.u8p)))
         return w, c != 0
 
-    def graph_edit(self, pre, post, weights, connected=None):
+    def graph_edit(self, pre, post, weights, connected=None, structure=False):
         """edit_weight for the pairs (pre[k], post[k]): Some(weights[k]) where connected[k] (None: everywhere), None elsewhere.  Applied
         as if one after another: of a pair listed twice the last wins.  A NaN weight of a connected pair is refused.
-        On a sparse handle the structure is fixed: connected[k] on a stored edge sets its weight and not connected[k] on an absent
-        pair is a no-op; connecting an absent pair or disconnecting a stored edge is refused (SnnError, BAD_ARG, the pair named)
-        before anything is written -- connect_sparse / set_graph_csr are what changes a structure."""
+        On a sparse handle the structure is fixed by default: connected[k] on a stored edge sets its weight and not connected[k] on
+        an absent pair is a no-op; connecting an absent pair or disconnecting a stored edge is refused (SnnError, BAD_ARG, the pair
+        named) before anything is written.  structure=True lifts that (snn_graph_csr_edit_structure): absent pairs are connected and
+        stored edges removed, merged on the device and committed as by set_graph_csr; kept edges keep their current weights, traces,
+        dw and counters, and the edge order of get_graph_csr is graph_csr_structure()'s afterwards.  A dense handle takes the
+        keyword and does what it always does: its edits are structural already."""
         p, q = self._pairs(pre, post)
         w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
         if np.ndim(weights) == 0:                # one weight for every pair
@@ -433,8 +437,14 @@ class DeviceNetwork:
         c = np.ones(p.size, np.uint8) if connected is None else np.ascontiguousarray(np.asarray(connected).reshape(-1) != 0, dtype=np.uint8)
         if w.size != p.size or c.size != p.size:
             raise ValueError("weights / connected must have one entry per pair")
-        self._check(self._graph_fn("edit")(self._h, p.ctypes.data_as(_lib.u32p), q.ctypes.data_as(_lib.u32p),
-                                           w.ctypes.data_as(_lib.f32p), c.ctypes.data_as(_lib.u8p), p.size))
+        sparse = getattr(self, "csr", False)
+        fn = self._L.snn_graph_csr_edit_structure if structure and sparse else self._graph_fn("edit")
+        self._check(fn(self._h, p.ctypes.data_as(_lib.u32p), q.ctypes.data_as(_lib.u32p), w.ctypes.data_as(_lib.f32p),
+                       c.ctypes.data_as(_lib.u8p), p.size))
+        if structure and sparse:
+            nnz = C.c_uint64()
+            self._check(self._L.snn_graph_csr_nnz(self._h, C.byref(nnz)))
+            self._nnz = int(nnz.value)
 
     def _graph_line(self, fn, which):
         n = C.c_uint64()
