@@ -2,8 +2,8 @@
 // lands, computed per element with no serial chain.  Integer arithmetic only; plain C++ that host and device code share, and that
 // tests/cpp/graph_merge_test.cpp includes alone.
 //
-// The edit list is sorted by (post, pre) with no pair twice (graph_merge_order: of a pair listed more than once the LAST
-// occurrence is kept).  Every edit is resolved against the stored row: it INSERTS (connected, not stored), REMOVES (not
+// The edit list is sorted by (post, pre) with no pair twice (graph_pairs_last_wins of snn_graph_pairs.hpp: of a pair listed more
+// than once the LAST occurrence is kept).  Every edit is resolved against the stored row: it INSERTS (connected, not stored), REMOVES (not
 // connected, stored), REWEIGHS (connected, stored) or does nothing (not connected, not stored).  ins_before / rem_before are the
 // exclusive prefix sums of the insert / remove flags over the sorted list, n_edits + 1 words each, so that the flag of edit t is
 // x_before[t + 1] - x_before[t] and a span [lo, t) holds x_before[t] - x_before[lo] of them.
@@ -84,21 +84,6 @@ SNN_MERGE_FN uint32_t graph_merge_insert_at(const uint32_t *ins_before, const ui
                                             uint32_t smaller)
 {
     return (ins_before[t] - ins_before[s.lo]) + smaller - (rem_before[t] - rem_before[s.lo]);
-}
-
-// Host only.  order[0 .. kept) = the positions in the call of the edits that count, ascending by (post, pre): of a pair listed
-// more than once the last occurrence.  `order` is any vector of uint64_t; returns kept.
-template <typename Vec>
-inline size_t graph_merge_order(const uint32_t *pre, const uint32_t *post, size_t n, Vec &order)
-{
-    order.resize(n);
-    for (size_t k = 0; k < n; ++k) order[k] = k;
-    auto key = [&](uint64_t k) { return ((uint64_t)post[k] << 32) | pre[k]; };
-    std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return key(a) != key(b) ? key(a) < key(b) : a < b; });
-    size_t kept = 0;
-    for (size_t k = 0; k < n; ++k)
-        if (k + 1 == n || key(order[k + 1]) != key(order[k])) order[kept++] = order[k];
-    return kept;
 }
 
 } // namespace snn

@@ -1,11 +1,14 @@
 // C ABI of the MI355X-native spiking-lattice stepper (include/snn_amd.h): the extern "C" entry points.  The one
 // translation unit of libsnn_amd.so: snn_network_state.hpp holds the handle (index space, device allocations,
 // attribute registry), snn_network_step.hpp the kernel launches and the step loop (snn_dispatch.hpp: which template
-// instantiation a launch takes), snn_network_verify.hpp the "verify" self-check of snn_run, snn_kernels_*.hpp the kernels.
+// instantiation a launch takes), snn_network_exchange.hpp the halo exchange between shards, snn_network_verify.hpp the "verify"
+// self-check of snn_run, snn_network_graph.hpp the bodies of the graph calls (graph setters, connect by rule, the Graph trait,
+// structural edits) and what they share -- their definitions here only pass the arguments on --, snn_kernels_*.hpp the kernels.
 #include "snn_network_state.hpp"
 #include "snn_network_step.hpp"
 #include "snn_network_exchange.hpp"
 #include "snn_network_verify.hpp"
+#include "snn_network_graph.hpp"
 
 // ================================================================================================
 // C ABI
@@ -269,40 +272,20 @@ int snn_get_attr_i32(snn_network_t *net, uint32_t id, const char *name, int32_t 
 { return attr_io(net, id, name, T_I32, dst, count, false); }
 ABI_CATCH
 
+// ---- the graph calls: bodies and what they share in snn_network_graph.hpp ----
 int snn_set_graph_rows(snn_network_t *net, uint32_t pre_begin, uint32_t pre_count, const float *weights,
                        const uint32_t *connections) ABI_TRY
-{
-    if (net) net->cross_checked = false;
-    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
-    return graph_rows_io(net, pre_begin, pre_count, const_cast<float *>(weights),
-                         const_cast<uint32_t *>(connections), net->nn, true);
-}
+{ return graph_io(net, true, false, pre_begin, pre_count, const_cast<float *>(weights), const_cast<uint32_t *>(connections), 0); }
 ABI_CATCH
 int snn_get_graph_rows(snn_network_t *net, uint32_t pre_begin, uint32_t pre_count, float *weights, uint32_t *connections) ABI_TRY
-{
-    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
-    return graph_rows_io(net, pre_begin, pre_count, weights, connections, net->nn, false);
-}
+{ return graph_io(net, false, false, pre_begin, pre_count, weights, connections, 0); }
 ABI_CATCH
 int snn_set_graph_dense(snn_network_t *net, const float *weights, const uint32_t *connections, size_t n_tot) ABI_TRY
-{
-    if (net) net->cross_checked = false;
-    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
-    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
-    if (n_tot != net->n_tot) return fail(SNN_ERR_DIM_MISMATCH, "graph size does not match the network");
-    return graph_rows_io(net, 0, net->n_tot, const_cast<float *>(weights), const_cast<uint32_t *>(connections),
-                         net->n_tot, true);
-}
+{ return graph_io(net, true, true, 0, 0, const_cast<float *>(weights), const_cast<uint32_t *>(connections), n_tot); }
 ABI_CATCH
 int snn_get_graph_dense(snn_network_t *net, float *weights, uint32_t *connections, size_t n_tot) ABI_TRY
-{
-    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
-    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
-    if (n_tot != net->n_tot) return fail(SNN_ERR_DIM_MISMATCH, "graph size does not match the network");
-    return graph_rows_io(net, 0, net->n_tot, weights, connections, net->n_tot, false);
-}
+{ return graph_io(net, false, true, 0, 0, weights, connections, n_tot); }
 ABI_CATCH
-
 int snn_fill_graph_synthetic(snn_network_t *net, uint64_t seed, float lo, float hi, int with_diagonal) ABI_TRY
 {
     if (net) net->cross_checked = false;
@@ -325,122 +308,6 @@ int snn_fill_graph_synthetic(snn_network_t *net, uint64_t seed, float lo, float 
     return SNN_OK;
 }
 ABI_CATCH
-
-// the arguments of one connection by rule, checked (snn_connect_by_rule; `where` = "record k: " for snn_connect_by_rules_csr)
-// weight_rules: how many weight rules the call takes (CONNECT_RULE_WEIGHTS; CONNECT_SPEC_WEIGHTS for the spec calls)
-static int connect_check(const snn_network *net, const std::string &where, uint32_t pre_id, uint32_t post_id, uint32_t rule, float probability,
-                         uint32_t weight_rule, float w_lo, float w_hi, const LatticeInfo **pre_out, const LatticeInfo **post_out,
-                         uint32_t weight_rules)
-{
-    const LatticeInfo *pre = find_lattice(net, pre_id), *post = find_lattice(net, post_id);
-    if (!pre) return fail(SNN_ERR_BAD_ARG, where + "pre_id: unknown lattice id " + std::to_string(pre_id));
-    if (!post) return fail(SNN_ERR_BAD_ARG, where + "post_id: unknown lattice id " + std::to_string(post_id));
-    if (post->spike_train)   // LatticeNetworkError::PostsynapticLatticeCannotBeSpikeTrain, neuron/mod.rs:1852-1854
-        return fail(SNN_ERR_BAD_ARG, where + "post_id: lattice " + std::to_string(post_id) + " is a spike-train lattice, which is never postsynaptic");
-    if (rule >= CONNECT_RULES) return fail(SNN_ERR_BAD_ARG, where + "rule: unknown connection rule " + std::to_string(rule));
-    if (weight_rule >= weight_rules) return fail(SNN_ERR_BAD_ARG, where + "weight_rule: unknown weight rule " + std::to_string(weight_rule));
-    if (probability != probability) return fail(SNN_ERR_BAD_ARG, where + "probability is NaN");
-    if (weight_rule == CONNECT_DISPLACEMENT) { *pre_out = pre; *post_out = post; return SNN_OK; }      // (w_lo, w_hi are not read)
-    if (w_lo - w_lo != 0.0f) return fail(SNN_ERR_BAD_ARG, where + "w_lo is not finite (NaN is the absent-edge sentinel of the device matrix)");
-    if (w_hi - w_hi != 0.0f) return fail(SNN_ERR_BAD_ARG, where + "w_hi is not finite (NaN is the absent-edge sentinel of the device matrix)");
-    if (weight_rule == CONNECT_UNIFORM && (w_hi - w_lo) - (w_hi - w_lo) != 0.0f)      // (lo + inf * u24 is +-inf, or NaN where u24 is 0)
-        return fail(SNN_ERR_BAD_ARG, where + "w_hi - w_lo is not finite: the uniform weights would be infinite or the absent-edge sentinel");
-    *pre_out = pre; *post_out = post;
-    return SNN_OK;
-}
-
-// what a spec adds to connect_check: the wrap flags, and for SNN_WEIGHT_DISPLACEMENT the table -- its dimensions follow from the
-// two grids and the flags, and every entry is finite or NaN (None).  `ext`: the kernels' form of it, the table still on the host.
-static int connect_spec_check(const snn_network *net, const std::string &where, const snn_connect_spec &s, const LatticeInfo **pre_out,
-                              const LatticeInfo **post_out, ConnectSpecExt *ext)
-{
-    const snn_connect_record &r = s.record;
-    TRY(connect_check(net, where, r.pre_id, r.post_id, r.rule, r.probability, r.weight_rule, r.w_lo, r.w_hi, pre_out, post_out, CONNECT_SPEC_WEIGHTS));
-    if (s.wrap > (SNN_WRAP_ROWS | SNN_WRAP_COLS)) return fail(SNN_ERR_BAD_ARG, where + "wrap: unknown flags " + std::to_string(s.wrap));
-    const LatticeInfo *pre = *pre_out, *post = *post_out;
-    *ext = ConnectSpecExt{};
-    ext->period_r = (s.wrap & SNN_WRAP_ROWS) ? std::max(pre->rows, post->rows) : 0u;
-    ext->period_c = (s.wrap & SNN_WRAP_COLS) ? std::max(pre->cols, post->cols) : 0u;
-    if (r.weight_rule != CONNECT_DISPLACEMENT) return SNN_OK;        // (table, table_rows and table_cols are not read)
-    ext->u_bias = pre->rows ? pre->rows - 1u : 0u;
-    ext->v_bias = pre->cols ? pre->cols - 1u : 0u;
-    const uint64_t rows = ext->period_r ? ext->period_r : (uint64_t)pre->rows + post->rows - (pre->rows && post->rows ? 1u : 0u);
-    const uint64_t cols = ext->period_c ? ext->period_c : (uint64_t)pre->cols + post->cols - (pre->cols && post->cols ? 1u : 0u);
-    if (!s.table) return fail(SNN_ERR_BAD_ARG, where + "table is null: SNN_WEIGHT_DISPLACEMENT reads its weights from it");
-    if (s.table_rows != rows)
-        return fail(SNN_ERR_BAD_ARG, where + "table_rows: " + std::to_string(s.table_rows) + " given, these lattices and flags take " + std::to_string(rows));
-    if (s.table_cols != cols)
-        return fail(SNN_ERR_BAD_ARG, where + "table_cols: " + std::to_string(s.table_cols) + " given, these lattices and flags take " + std::to_string(cols));
-    for (uint64_t k = 0; k < rows * cols; ++k)
-        if (s.table[k] == s.table[k] && s.table[k] - s.table[k] != 0.0f)
-            return fail(SNN_ERR_BAD_ARG, where + "table: entry " + std::to_string(k) + " is infinite (a weight is finite; NaN marks the pairs without an edge)");
-    ext->table_cols = s.table_cols;
-    return SNN_OK;
-}
-
-// the table of a checked spec in a device buffer of the handle's allocator (the caller's dev_ptr frees it); ext->table points at it
-static int connect_spec_upload(snn_network *net, const snn_connect_spec &s, ConnectSpecExt *ext, dev_ptr<float> *table_d)
-{
-    if (s.record.weight_rule != CONNECT_DISPLACEMENT) return SNN_OK;
-    const size_t bytes = (size_t)s.table_rows * s.table_cols * 4;
-    HIP_TRY(snn_malloc(table_d, std::max<size_t>(bytes, 256)), SNN_ERR_BUFFER_CREATE);
-    if (bytes) HIP_TRY(copy_sync(net, table_d->get(), s.table, bytes, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-    ext->table = table_d->get();
-    return SNN_OK;
-}
-
-// snn_connect_by_rule and snn_connect_by_spec: one body.  A plain spec (no table, no distance on a ring) launches k_connect_rule.
-static int connect_dense(snn_network_t *net, const snn_connect_spec &s, uint32_t weight_rules)
-{
-    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
-    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
-    if (net->csr) return fail(SNN_ERR_BAD_STATE, "connecting by rule is for dense handles only: this handle holds a sparse graph");
-    const snn_connect_record &r = s.record;
-    const LatticeInfo *pre = nullptr, *post = nullptr;
-    ConnectSpecExt x{};
-    if (weight_rules == CONNECT_RULE_WEIGHTS)
-        TRY(connect_check(net, "", r.pre_id, r.post_id, r.rule, r.probability, r.weight_rule, r.w_lo, r.w_hi, &pre, &post, CONNECT_RULE_WEIGHTS));
-    else
-        TRY(connect_spec_check(net, "", s, &pre, &post, &x));
-    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
-    TRY(end_run(net));                     // a deferred reward-modulated update belongs to the OLD weights: apply it first
-    dev_ptr<float> table_d;                // (freed when the call returns; a failure here leaves the graph as it was)
-    TRY(connect_spec_upload(net, s, &x, &table_d));
-    net->cross_checked = false;
-    net->cache.counts_dirty = true;        // stale from here on, whichever way the call ends (as graph_rows_io marks them on every exit of a set)
-    w24_invalidate(net);
-    // the block's columns this handle owns, as local columns
-    const uint32_t c_begin = std::max(post->first, net->q0), c_end = std::min(post->first + post->count, net->q0 + net->n_loc);
-    if (pre->count && c_begin < c_end) {
-        ConnectArgs a{};
-        a.W = net->W; a.ld = net->ld;
-        a.col0 = c_begin - net->q0; a.n_cols = c_end - c_begin; a.post_i0 = c_begin - post->first;
-        a.post_cols = post->cols; a.post_count = post->count;
-        a.pre_first = pre->first; a.pre_count = pre->count; a.pre_rows = pre->rows; a.pre_cols = pre->cols;
-        a.extent = r.extent; a.probability = r.probability; a.edge_seed = r.edge_seed; a.weight_seed = r.weight_seed;
-        a.w_lo = r.w_lo; a.w_hi = r.w_hi;
-        const uint32_t groups = ((a.pre_first + a.pre_count - 1u) >> 2) - (a.pre_first >> 2) + 1u;
-        const uint32_t blocks_x = (a.col0 + a.n_cols - (a.col0 & ~63u) + 255u) / 256u;
-        const dim3 grid(blocks_x, std::min<uint32_t>(groups, 4096));
-        const bool thin = r.probability < 1.0f, self = r.self_edges != 0, wrap = x.period_r || x.period_c;
-        // (probability <= 0: the draw is made and never succeeds)
-        if (connect_spec_is_plain((int)r.rule, (int)r.weight_rule, wrap))
-            hipLaunchKernelGGL(connect_kernel((int)r.rule, (int)r.weight_rule, thin, self), grid, dim3(256), 0, net->stream, a);
-        else
-            hipLaunchKernelGGL(connect_spec_kernel((int)r.rule, (int)r.weight_rule, wrap, thin, self), grid, dim3(256), 0, net->stream,
-                               ConnectSpecArgs{a, x});
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        // a replaced edge starts with a fresh TraceRSTDP; the other blocks keep theirs
-        for (float *m : {net->trace.get(), net->pending.get(), net->edge_counter.get()})
-            if (m) {
-                hipLaunchKernelGGL(k_connect_clear, grid, dim3(256), 0, net->stream, m, net->ld, a.col0, a.n_cols, a.pre_first, a.pre_count);
-                HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-            }
-        HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
-    }
-    return SNN_OK;
-}
-
 int snn_connect_by_rule(snn_network_t *net, uint32_t pre_id, uint32_t post_id, uint32_t rule, uint32_t extent,
                         int self_edges, float probability, uint64_t edge_seed, uint32_t weight_rule, float w_lo,
                         float w_hi, uint64_t weight_seed) ABI_TRY
@@ -450,392 +317,44 @@ int snn_connect_by_rule(snn_network_t *net, uint32_t pre_id, uint32_t post_id, u
     return connect_dense(net, s, CONNECT_RULE_WEIGHTS);
 }
 ABI_CATCH
-
 int snn_connect_by_spec(snn_network_t *net, const snn_connect_spec *spec) ABI_TRY
 {
     if (!spec) return fail(SNN_ERR_BAD_ARG, "spec is null");
     return connect_dense(net, *spec, CONNECT_SPEC_WEIGHTS);
 }
 ABI_CATCH
-
-// ---- the Graph trait on a dense handle (graph/mod.rs:42-72): lookup_weight, edit_weight, incoming / outgoing connections ----
-// what the four calls check first, as graph_rows_io does
-static int graph_query_begin(const snn_network *net)
-{
-    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
-    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
-    if (net->csr)
-        return fail(SNN_ERR_BAD_STATE, "handle holds a CSR graph, whose structure is fixed: read it with snn_get_graph_csr_structure / "
-                                       "snn_get_graph_csr (12 bytes per edge on the host)");
-    return SNN_OK;
-}
-// one index pair of a call: inside the matrix, and in a column this handle owns (`what`: "pair k" / "post")
-static int graph_pair_check(const snn_network *net, const std::string &what, uint32_t pre, uint32_t post)
-{
-    const std::string where = what + " (pre " + std::to_string(pre) + ", post " + std::to_string(post) + "): ";
-    if (pre >= net->n_tot) return fail(SNN_ERR_BAD_ARG, where + "pre is not below n_tot = " + std::to_string(net->n_tot));
-    if (post >= net->nn) return fail(SNN_ERR_BAD_ARG, where + "post is not below n_neurons = " + std::to_string(net->nn));
-    if (post < net->q0 || post >= net->q0 + net->n_loc)
-        return fail(SNN_ERR_BAD_ARG, where + "post is outside the columns this shard owns, [" + std::to_string(net->q0) + ", " +
-                                     std::to_string(net->q0 + net->n_loc) + ")");
-    return SNN_OK;
-}
-constexpr size_t GRAPH_PAIRS_HOP = (size_t)1 << 20;         // pairs per launch: the device lists of a call hold no more
-
+// the Graph trait (graph/mod.rs:42-72) on a dense handle ...
 int snn_graph_lookup(snn_network_t *net, const uint32_t *pre, const uint32_t *post, size_t n, float *weights, uint8_t *connected) ABI_TRY
-{
-    TRY(graph_query_begin(net));
-    if (n == 0) return SNN_OK;
-    if (!pre || !post || !weights || !connected) return fail(SNN_ERR_BAD_ARG, "null pointer with n > 0");
-    for (size_t k = 0; k < n; ++k)
-        if (pre[k] >= net->n_tot || post[k] - net->q0 >= net->n_loc) return graph_pair_check(net, "pair " + std::to_string(k), pre[k], post[k]);
-    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
-    TRY(end_run(net));                     // deferred STDP / R-STDP updates belong to the weights a lookup sees
-    const size_t hop = std::min(n, GRAPH_PAIRS_HOP);
-    dev_ptr<uint32_t> pre_d, post_d;
-    dev_ptr<float> w_d;
-    dev_ptr<uint8_t> c_d;
-    HIP_TRY(snn_malloc(&pre_d, hop * 4), SNN_ERR_BUFFER_CREATE);
-    HIP_TRY(snn_malloc(&post_d, hop * 4), SNN_ERR_BUFFER_CREATE);
-    HIP_TRY(snn_malloc(&w_d, hop * 4), SNN_ERR_BUFFER_CREATE);
-    HIP_TRY(snn_malloc(&c_d, std::max<size_t>(hop, 256)), SNN_ERR_BUFFER_CREATE);
-    for (size_t k = 0; k < n; k += hop) {
-        const uint32_t m = (uint32_t)std::min(hop, n - k);
-        HIP_TRY(copy_sync(net, pre_d, pre + k, (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        HIP_TRY(copy_sync(net, post_d, post + k, (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        hipLaunchKernelGGL(k_graph_lookup, dim3((m + 255u) / 256u), dim3(256), 0, net->stream, net->W, net->ld, net->q0, pre_d, post_d, m,
-                           w_d, c_d);
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        HIP_TRY(copy_sync(net, weights + k, w_d, (size_t)m * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-        HIP_TRY(copy_sync(net, connected + k, c_d, m, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-    }
-    return SNN_OK;
-}
+{ return graph_lookup(net, false, pre, post, n, weights, connected); }
 ABI_CATCH
-
 int snn_graph_edit(snn_network_t *net, const uint32_t *pre, const uint32_t *post, const float *weights, const uint8_t *connected,
                    size_t n) ABI_TRY
-{
-    TRY(graph_query_begin(net));
-    if (n == 0) return SNN_OK;
-    if (!pre || !post || !weights || !connected) return fail(SNN_ERR_BAD_ARG, "null pointer with n > 0");
-    // every pair is checked before anything is written: a refused call leaves the graph as it was
-    bool ascending = true;                 // strictly, by (pre, post): no pair twice
-    for (size_t k = 0; k < n; ++k) {
-        if (pre[k] >= net->n_tot || post[k] - net->q0 >= net->n_loc) return graph_pair_check(net, "pair " + std::to_string(k), pre[k], post[k]);
-        if (connected[k] && weights[k] != weights[k])
-            return fail(SNN_ERR_BAD_ARG, "pair " + std::to_string(k) + " (pre " + std::to_string(pre[k]) + ", post " + std::to_string(post[k]) +
-                                         "): a connected edge carries a NaN weight; NaN is the absent-edge sentinel of the device matrix, such "
-                                         "an edge cannot be stored (graph/mod.rs:204-213).  Nothing of this call was applied");
-        if (k && (pre[k] < pre[k - 1] || (pre[k] == pre[k - 1] && post[k] <= post[k - 1]))) ascending = false;
-    }
-    // "as if one after another": of a pair that occurs more than once the LAST occurrence is kept, decided here -- every element is
-    // written by one thread, whatever the order the threads run in
-    hvec<uint64_t> order;
-    size_t kept = n;
-    if (!ascending) {
-        order.resize(n);
-        for (size_t k = 0; k < n; ++k) order[k] = k;
-        auto key = [&](uint64_t k) { return ((uint64_t)pre[k] << 32) | post[k]; };
-        std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return key(a) != key(b) ? key(a) < key(b) : a < b; });
-        kept = 0;
-        for (size_t k = 0; k < n; ++k)
-            if (k + 1 == n || key(order[k + 1]) != key(order[k])) order[kept++] = order[k];
-    }
-    const size_t hop = std::min(kept, GRAPH_PAIRS_HOP);
-    hvec<uint32_t> pre_h(hop), post_h(hop);
-    hvec<float> value_h(hop);
-    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
-    TRY(end_run(net));                     // a deferred update belongs to the OLD weights: applied now, it cannot overwrite the edit
-    dev_ptr<uint32_t> pre_d, post_d;
-    dev_ptr<float> value_d;
-    HIP_TRY(snn_malloc(&pre_d, hop * 4), SNN_ERR_BUFFER_CREATE);
-    HIP_TRY(snn_malloc(&post_d, hop * 4), SNN_ERR_BUFFER_CREATE);
-    HIP_TRY(snn_malloc(&value_d, hop * 4), SNN_ERR_BUFFER_CREATE);
-    if (net->opt.pinned_copies && !net->copy_stage)           // (the staging buffer of copy_sync: allocated before the first write)
-        HIP_TRY(host_malloc(&net->copy_stage, (size_t)8 << 20, hipHostMallocDefault), SNN_ERR_BUFFER_CREATE);
-    net->cross_checked = false;
-    net->cache.counts_dirty = true;        // stale from here on, whichever way the call ends
-    w24_invalidate(net);
-    const float absent = std::nanf("");
-    for (size_t k = 0; k < kept; k += hop) {
-        const uint32_t m = (uint32_t)std::min(hop, kept - k);
-        for (uint32_t j = 0; j < m; ++j) {
-            const size_t src = ascending ? k + j : (size_t)order[k + j];
-            pre_h[j] = pre[src]; post_h[j] = post[src];
-            value_h[j] = connected[src] ? weights[src] : absent;
-        }
-        HIP_TRY(copy_sync(net, pre_d, pre_h.data(), (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        HIP_TRY(copy_sync(net, post_d, post_h.data(), (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        HIP_TRY(copy_sync(net, value_d, value_h.data(), (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        hipLaunchKernelGGL(k_graph_edit, dim3((m + 255u) / 256u), dim3(256), 0, net->stream, net->W, net->trace.get(), net->pending.get(),
-                           net->edge_counter.get(), net->ld, net->q0, pre_d, post_d, value_d, m);
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
-    }
-    return SNN_OK;
-}
+{ return graph_edit(net, pre, post, weights, connected, n); }
 ABI_CATCH
-
-// one column (incoming) or one row (outgoing) of W as ascending (index, weight) lists: the two-call idiom of snn_halo_needs
-static int graph_line(snn_network *net, bool column, uint32_t line, uint32_t *index, float *weights, uint64_t capacity, uint64_t *count)
-{
-    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
-    TRY(end_run(net));
-    const uint32_t n = column ? net->n_tot : net->n_loc;
-    if (n == 0 || net->n_loc == 0) return SNN_OK;
-    const uint32_t room = index && weights ? (uint32_t)std::min<uint64_t>(capacity, n) : 0u;
-    dev_ptr<uint32_t> index_d, count_d;
-    dev_ptr<float> w_d;
-    HIP_TRY(snn_malloc(&index_d, std::max<size_t>((size_t)room * 4, 256)), SNN_ERR_BUFFER_CREATE);
-    HIP_TRY(snn_malloc(&w_d, std::max<size_t>((size_t)room * 4, 256)), SNN_ERR_BUFFER_CREATE);
-    HIP_TRY(snn_malloc(&count_d, 256), SNN_ERR_BUFFER_CREATE);
-    hipLaunchKernelGGL(column ? k_graph_line<true> : k_graph_line<false>, dim3(1), dim3(256), 0, net->stream, net->W, net->ld, net->q0, line, n,
-                       index_d, w_d, room, count_d);
-    HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-    uint32_t found = 0;
-    HIP_TRY(copy_sync(net, &found, count_d, 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-    *count = found;
-    if (found == 0 || found > capacity) return SNN_OK;
-    if (!index || !weights) return fail(SNN_ERR_BAD_ARG, "null list pointer with capacity >= count > 0");
-    HIP_TRY(copy_sync(net, index, index_d, (size_t)found * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-    HIP_TRY(copy_sync(net, weights, w_d, (size_t)found * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-    return SNN_OK;
-}
-
 int snn_graph_incoming(snn_network_t *net, uint32_t post, uint32_t *pre_index, float *weights, uint64_t capacity, uint64_t *count) ABI_TRY
-{
-    TRY(graph_query_begin(net));
-    if (!count) return fail(SNN_ERR_BAD_ARG, "count is null");
-    *count = 0;
-    if (post >= net->nn) return fail(SNN_ERR_BAD_ARG, "post " + std::to_string(post) + " is not below n_neurons = " + std::to_string(net->nn));
-    if (post < net->q0 || post >= net->q0 + net->n_loc)
-        return fail(SNN_ERR_BAD_ARG, "post " + std::to_string(post) + " is outside the columns this shard owns, [" + std::to_string(net->q0) +
-                                     ", " + std::to_string(net->q0 + net->n_loc) + ")");
-    return graph_line(net, true, post - net->q0, pre_index, weights, capacity, count);
-}
+{ return graph_line_query(net, false, true, post, pre_index, weights, capacity, count); }
 ABI_CATCH
-
 int snn_graph_outgoing(snn_network_t *net, uint32_t pre, uint32_t *post_index, float *weights, uint64_t capacity, uint64_t *count) ABI_TRY
-{
-    TRY(graph_query_begin(net));
-    if (!count) return fail(SNN_ERR_BAD_ARG, "count is null");
-    *count = 0;
-    if (pre >= net->n_tot) return fail(SNN_ERR_BAD_ARG, "pre " + std::to_string(pre) + " is not below n_tot = " + std::to_string(net->n_tot));
-    return graph_line(net, false, pre, post_index, weights, capacity, count);
-}
+{ return graph_line_query(net, false, false, pre, post_index, weights, capacity, count); }
 ABI_CATCH
-
-// ---- the Graph trait on a sparse handle (graph/mod.rs:42-72), on the SELL-64 arrays and the transpose as they lie on the device:
-// no table of size nnz is read, built or moved by any of the four (no edge_slot_host, no download of the SELL arrays) ----
-static int graph_csr_begin(const snn_network *net)
-{
-    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
-    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
-    if (!net->csr)
-        return fail(SNN_ERR_BAD_STATE, "handle holds a dense graph: ask it with snn_graph_lookup / snn_graph_edit / snn_graph_incoming / "
-                                       "snn_graph_outgoing");
-    if (net->block_mode) return fail(SNN_ERR_BAD_STATE, "the graph queries do not cover shards by lattice (range-set ownership): not covered");
-    return SNN_OK;
-}
-static std::string graph_csr_pair(size_t k, uint32_t pre, uint32_t post)
-{
-    return "pair " + std::to_string(k) + " (pre " + std::to_string(pre) + ", post " + std::to_string(post) + ")";
-}
-static int graph_csr_fixed(size_t k, uint32_t pre, uint32_t post, bool connect)
-{
-    return fail(SNN_ERR_BAD_ARG, graph_csr_pair(k, pre, post) + (connect ? ": no stored edge, and an edit cannot connect it" : ": a stored edge, and an edit cannot remove it") +
-                                     ": the structure of a sparse graph is fixed (snn_connect_by_rules_csr / snn_set_graph_csr replace it).  "
-                                     "Nothing of this call was applied");
-}
-
+// ... and on a sparse one; snn_graph_csr_edit_structure: edit_weight in full, edges connected and removed
 int snn_graph_csr_lookup(snn_network_t *net, const uint32_t *pre, const uint32_t *post, size_t n, float *weights, uint8_t *connected) ABI_TRY
-{
-    TRY(graph_csr_begin(net));
-    if (n == 0) return SNN_OK;
-    if (!pre || !post || !weights || !connected) return fail(SNN_ERR_BAD_ARG, "null pointer with n > 0");
-    for (size_t k = 0; k < n; ++k)
-        if (pre[k] >= net->n_tot || post[k] - net->q0 >= net->n_loc) return graph_pair_check(net, "pair " + std::to_string(k), pre[k], post[k]);
-    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
-    TRY(end_run(net));                     // deferred STDP / R-STDP updates belong to the weights a lookup sees
-    if (!net->csr_ptr) {                   // no graph set yet: the empty one
-        std::fill(weights, weights + n, 0.0f);
-        std::fill(connected, connected + n, (uint8_t)0);
-        return SNN_OK;
-    }
-    const size_t hop = std::min(n, GRAPH_PAIRS_HOP);
-    dev_ptr<uint32_t> pre_d, post_d;
-    dev_ptr<float> w_d;
-    dev_ptr<uint8_t> c_d;
-    HIP_TRY(snn_malloc(&pre_d, hop * 4), SNN_ERR_BUFFER_CREATE);
-    HIP_TRY(snn_malloc(&post_d, hop * 4), SNN_ERR_BUFFER_CREATE);
-    HIP_TRY(snn_malloc(&w_d, hop * 4), SNN_ERR_BUFFER_CREATE);
-    HIP_TRY(snn_malloc(&c_d, std::max<size_t>(hop, 256)), SNN_ERR_BUFFER_CREATE);
-    for (size_t k = 0; k < n; k += hop) {
-        const uint32_t m = (uint32_t)std::min(hop, n - k);
-        HIP_TRY(copy_sync(net, pre_d, pre + k, (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        HIP_TRY(copy_sync(net, post_d, post + k, (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        hipLaunchKernelGGL(k_graph_csr_find, dim3((m + 255u) / 256u), dim3(256), 0, net->stream, (const uint32_t *)net->csr_ptr,
-                           (const uint32_t *)net->csr_pre, (const float *)net->csr_w, (const uint32_t *)net->csr_row_len, net->q0,
-                           (const uint32_t *)pre_d, (const uint32_t *)post_d, m, (uint32_t *)nullptr, w_d.get(), c_d.get(),
-                           (const uint8_t *)nullptr, 0ull, (unsigned long long *)nullptr);
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        HIP_TRY(copy_sync(net, weights + k, w_d, (size_t)m * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-        HIP_TRY(copy_sync(net, connected + k, c_d, m, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-    }
-    return SNN_OK;
-}
+{ return graph_lookup(net, true, pre, post, n, weights, connected); }
 ABI_CATCH
-
 int snn_graph_csr_edit(snn_network_t *net, const uint32_t *pre, const uint32_t *post, const float *weights, const uint8_t *connected,
                        size_t n) ABI_TRY
-{
-    TRY(graph_csr_begin(net));
-    if (n == 0) return SNN_OK;
-    if (!pre || !post || !weights || !connected) return fail(SNN_ERR_BAD_ARG, "null pointer with n > 0");
-    // every pair is checked before anything is written: a refused call leaves the graph as it was
-    bool ascending = true;                 // strictly, by (pre, post): no pair twice
-    for (size_t k = 0; k < n; ++k) {
-        if (pre[k] >= net->n_tot || post[k] - net->q0 >= net->n_loc) return graph_pair_check(net, "pair " + std::to_string(k), pre[k], post[k]);
-        if (connected[k] && weights[k] != weights[k])
-            return fail(SNN_ERR_BAD_ARG, graph_csr_pair(k, pre[k], post[k]) + ": a connected edge carries a NaN weight; NaN is the absent-edge "
-                                         "sentinel of the dense form, which the sparse form refuses alike (graph/mod.rs:204-213).  Nothing of "
-                                         "this call was applied");
-        if (k && (pre[k] < pre[k - 1] || (pre[k] == pre[k - 1] && post[k] <= post[k - 1]))) ascending = false;
-    }
-    if (!net->csr_ptr) {                   // no graph set yet: every pair is absent, and stays so
-        for (size_t k = 0; k < n; ++k)
-            if (connected[k]) return graph_csr_fixed(k, pre[k], post[k], true);
-        return SNN_OK;
-    }
-    // "as if one after another": the structure never changes, so every occurrence of a pair is held to the rule on its own (the
-    // resolve pass, in the order of the call), and of a pair that occurs more than once the LAST occurrence is written, decided
-    // here -- every entry is written by one thread, whatever the order the threads run in
-    hvec<uint64_t> order;
-    size_t kept = n;
-    if (!ascending) {
-        order.resize(n);
-        for (size_t k = 0; k < n; ++k) order[k] = k;
-        auto key = [&](uint64_t k) { return ((uint64_t)pre[k] << 32) | post[k]; };
-        std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return key(a) != key(b) ? key(a) < key(b) : a < b; });
-        kept = 0;
-        for (size_t k = 0; k < n; ++k)
-            if (k + 1 == n || key(order[k + 1]) != key(order[k])) order[kept++] = order[k];
-    }
-    const size_t hop = std::min(n, GRAPH_PAIRS_HOP);
-    hvec<float> value_h(ascending ? 0 : hop);
-    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
-    TRY(end_run(net));                     // a deferred update belongs to the OLD weights: applied now, it cannot overwrite the edit
-    dev_ptr<uint32_t> pre_d, post_d, slot_d;
-    dev_ptr<uint8_t> want_d;
-    dev_ptr<float> value_d;
-    dev_ptr<unsigned long long> sel_d, bad_d;
-    HIP_TRY(snn_malloc(&pre_d, hop * 4), SNN_ERR_BUFFER_CREATE);
-    HIP_TRY(snn_malloc(&post_d, hop * 4), SNN_ERR_BUFFER_CREATE);
-    HIP_TRY(snn_malloc(&want_d, std::max<size_t>(hop, 256)), SNN_ERR_BUFFER_CREATE);
-    HIP_TRY(snn_malloc(&slot_d, n * 4), SNN_ERR_BUFFER_CREATE);            // the entry of every pair of the call, in its order
-    HIP_TRY(snn_malloc(&value_d, hop * 4), SNN_ERR_BUFFER_CREATE);
-    if (!ascending) HIP_TRY(snn_malloc(&sel_d, hop * 8), SNN_ERR_BUFFER_CREATE);
-    HIP_TRY(snn_malloc(&bad_d, 256), SNN_ERR_BUFFER_CREATE);
-    if (net->opt.pinned_copies && !net->copy_stage)           // (the staging buffer of copy_sync: allocated before the first write)
-        HIP_TRY(host_malloc(&net->copy_stage, (size_t)8 << 20, hipHostMallocDefault), SNN_ERR_BUFFER_CREATE);
-    // ---- the resolve pass: read only ----
-    unsigned long long bad = GRAPH_CSR_ALL_FINE;
-    HIP_TRY(copy_sync(net, bad_d, &bad, 8, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-    for (size_t k = 0; k < n; k += hop) {
-        const uint32_t m = (uint32_t)std::min(hop, n - k);
-        HIP_TRY(copy_sync(net, pre_d, pre + k, (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        HIP_TRY(copy_sync(net, post_d, post + k, (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        HIP_TRY(copy_sync(net, want_d, connected + k, m, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        hipLaunchKernelGGL(k_graph_csr_find, dim3((m + 255u) / 256u), dim3(256), 0, net->stream, (const uint32_t *)net->csr_ptr,
-                           (const uint32_t *)net->csr_pre, (const float *)net->csr_w, (const uint32_t *)net->csr_row_len, net->q0,
-                           (const uint32_t *)pre_d, (const uint32_t *)post_d, m, slot_d.get() + k, (float *)nullptr, (uint8_t *)nullptr,
-                           (const uint8_t *)want_d, (unsigned long long)k, bad_d.get());
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
-    }
-    HIP_TRY(copy_sync(net, &bad, bad_d, 8, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-    if (bad != GRAPH_CSR_ALL_FINE) {
-        if (bad >= n) return fail(SNN_ERR_BAD_STATE, "the resolve pass named a pair the call does not have");
-        return graph_csr_fixed((size_t)bad, pre[bad], post[bad], connected[bad] != 0);
-    }
-    // ---- the write pass ----
-    net->cross_checked = false;
-    net->img_stale = net->img_stale_direct = true;             // the step image's records are packed again before the next image step
-    for (size_t k = 0; k < kept; k += hop) {
-        const uint32_t m = (uint32_t)std::min(hop, kept - k);
-        if (ascending) {
-            HIP_TRY(copy_sync(net, value_d, weights + k, (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        } else {
-            for (uint32_t j = 0; j < m; ++j) value_h[j] = weights[order[k + j]];
-            HIP_TRY(copy_sync(net, value_d, value_h.data(), (size_t)m * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-            HIP_TRY(copy_sync(net, sel_d, order.data() + k, (size_t)m * 8, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        }
-        hipLaunchKernelGGL(k_graph_csr_store, dim3((m + 255u) / 256u), dim3(256), 0, net->stream, net->csr_w.get(), net->trace.get(),
-                           net->pending.get(), net->edge_counter.get(), (const uint32_t *)(ascending ? slot_d.get() + k : slot_d.get()),
-                           (const unsigned long long *)sel_d.get(), (const float *)value_d, m);
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
-    }
-    return SNN_OK;
-}
+{ return graph_csr_edit(net, pre, post, weights, connected, n); }
 ABI_CATCH
-
-// one row of the SELL arrays (incoming) or one source of the transpose (outgoing) as ascending (index, weight) lists: the count
-// is one or two words read from the device, the lists are copied when there is room for them
-static int graph_csr_line(snn_network *net, bool incoming, uint32_t line, uint32_t *index, float *weights, uint64_t capacity, uint64_t *count)
-{
-    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
-    TRY(end_run(net));
-    if (!net->csr_ptr || net->n_loc == 0) return SNN_OK;          // no graph set yet: the empty one
-    uint32_t span[2] = {0, 0};
-    if (incoming) HIP_TRY(copy_sync(net, &span[1], net->csr_row_len.get() + line, 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-    else HIP_TRY(copy_sync(net, span, net->csr_t_ptr.get() + line, 8, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-    if (span[1] < span[0]) return fail(SNN_ERR_BAD_STATE, "the stored transpose offsets are not monotone");
-    const uint32_t found = span[1] - span[0];
-    *count = found;
-    if (found == 0 || found > capacity) return SNN_OK;
-    if (!index || !weights) return fail(SNN_ERR_BAD_ARG, "null list pointer with capacity >= count > 0");
-    dev_ptr<uint32_t> index_d;
-    dev_ptr<float> w_d;
-    HIP_TRY(snn_malloc(&index_d, std::max<size_t>((size_t)found * 4, 256)), SNN_ERR_BUFFER_CREATE);
-    HIP_TRY(snn_malloc(&w_d, std::max<size_t>((size_t)found * 4, 256)), SNN_ERR_BUFFER_CREATE);
-    const dim3 grid(std::min<uint32_t>((found + 255u) / 256u, 1024u));
-    if (incoming)
-        hipLaunchKernelGGL(k_graph_csr_row, grid, dim3(256), 0, net->stream, (const uint32_t *)net->csr_ptr, (const uint32_t *)net->csr_pre,
-                           (const float *)net->csr_w, line, found, index_d.get(), w_d.get());
-    else
-        hipLaunchKernelGGL(k_graph_csr_out, grid, dim3(256), 0, net->stream, (const uint32_t *)net->csr_t_edge, (const uint32_t *)net->csr_post,
-                           (const uint32_t *)net->csr_edge_slot, (const float *)net->csr_w, net->q0, span[0], found, index_d.get(), w_d.get());
-    HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-    HIP_TRY(copy_sync(net, index, index_d, (size_t)found * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-    HIP_TRY(copy_sync(net, weights, w_d, (size_t)found * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-    return SNN_OK;
-}
-
 int snn_graph_csr_incoming(snn_network_t *net, uint32_t post, uint32_t *pre_index, float *weights, uint64_t capacity, uint64_t *count) ABI_TRY
-{
-    TRY(graph_csr_begin(net));
-    if (!count) return fail(SNN_ERR_BAD_ARG, "count is null");
-    *count = 0;
-    if (post >= net->nn) return fail(SNN_ERR_BAD_ARG, "post " + std::to_string(post) + " is not below n_neurons = " + std::to_string(net->nn));
-    if (post < net->q0 || post >= net->q0 + net->n_loc)
-        return fail(SNN_ERR_BAD_ARG, "post " + std::to_string(post) + " is outside the columns this shard owns, [" + std::to_string(net->q0) +
-                                     ", " + std::to_string(net->q0 + net->n_loc) + ")");
-    return graph_csr_line(net, true, post - net->q0, pre_index, weights, capacity, count);
-}
+{ return graph_line_query(net, true, true, post, pre_index, weights, capacity, count); }
 ABI_CATCH
-
 int snn_graph_csr_outgoing(snn_network_t *net, uint32_t pre, uint32_t *post_index, float *weights, uint64_t capacity, uint64_t *count) ABI_TRY
-{
-    TRY(graph_csr_begin(net));
-    if (!count) return fail(SNN_ERR_BAD_ARG, "count is null");
-    *count = 0;
-    if (pre >= net->n_tot) return fail(SNN_ERR_BAD_ARG, "pre " + std::to_string(pre) + " is not below n_tot = " + std::to_string(net->n_tot));
-    return graph_csr_line(net, false, pre, post_index, weights, capacity, count);
-}
+{ return graph_line_query(net, true, false, pre, post_index, weights, capacity, count); }
 ABI_CATCH
-
+int snn_graph_csr_edit_structure(snn_network_t *net, const uint32_t *pre, const uint32_t *post, const float *weights,
+                                 const uint8_t *connected, size_t n) ABI_TRY
+{ return graph_csr_edit_structure(net, pre, post, weights, connected, n); }
+ABI_CATCH
 int snn_network_use_csr(snn_network_t *net, int enable) ABI_TRY
 {
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
@@ -844,157 +363,6 @@ int snn_network_use_csr(snn_network_t *net, int enable) ABI_TRY
     return SNN_OK;
 }
 ABI_CATCH
-
-namespace { int ensure_traces(snn_network *net); int ensure_pending(snn_network *net); }
-
-// All or nothing: a failed call leaves the previous graph in place, intact -- except that the traces / dw / counters of a handle
-// with modulation or connection kinds are sized by the new graph and allocated after the commit: if THAT fails, the handle holds
-// the new graph without them.  Device memory peaks at old graph + new graph while the call runs.
-// `keep` (may be null): at the commit the planes of the replaced edges move there instead of being freed -- a structural edit
-// carries them over to the edges it keeps (snn_graph_csr_edit_structure).  Untouched when the call fails before the commit.
-struct CsrEdgePlanes { dev_ptr<float> trace, pending, edge_counter; };
-
-static int set_graph_csr_impl(snn_network_t *net, const uint64_t *row_ptr, const uint32_t *pre_index, const float *weights,
-                              uint64_t nnz, CsrEdgePlanes *keep = nullptr)
-{
-    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
-    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
-    if (!net->csr) return fail(SNN_ERR_BAD_STATE, "handle holds a dense graph: call snn_network_use_csr before finalize");
-    if (!row_ptr || (nnz && (!pre_index || !weights))) return fail(SNN_ERR_BAD_ARG, "null graph pointer");
-    if (nnz >= 0xFFFFFFFFull) return fail(SNN_ERR_DIM_MISMATCH, "more than 2^32-1 stored synapses per handle");
-    if ((uint64_t)net->nn + net->nc >= PLAN_CODE) return fail(SNN_ERR_DIM_MISMATCH, "the gather plan addresses fewer than 2^31-1 presynaptic rows");
-    // the caller's rows are the OWNED neurons in ascending order; a range-set shard places them on its local rows
-    // (global 64-blocks, holes in between keep length 0)
-    const uint32_t n_loc = net->n_loc, n_rows = net->n_owned;
-    auto local = [&](uint32_t k) { return net->block_mode ? net->owned_local_host[k] : k; };
-    if (row_ptr[0] != 0 || row_ptr[n_rows] != nnz) return fail(SNN_ERR_DIM_MISMATCH, "row_ptr must run from 0 to nnz");
-    const uint32_t n_slices = (n_loc + 63) / 64;
-    hvec<uint32_t> slice_ptr((size_t)n_slices + 1, 0), row_len((size_t)n_slices * 64, 0), post(nnz),
-        t_ptr((size_t)net->n_tot + 1, 0), t_edge(nnz), edge_slot(nnz);
-    for (uint32_t k = 0; k < n_rows; ++k) {
-        const uint32_t q = local(k);
-        if (row_ptr[k + 1] < row_ptr[k]) return fail(SNN_ERR_DIM_MISMATCH, "row_ptr is not monotone");
-        row_len[q] = (uint32_t)(row_ptr[k + 1] - row_ptr[k]);
-        for (uint64_t e = row_ptr[k]; e < row_ptr[k + 1]; ++e) {
-            if (pre_index[e] >= net->n_tot) return fail(SNN_ERR_DIM_MISMATCH, "presynaptic index out of range");
-            if (e > row_ptr[k] && pre_index[e] <= pre_index[e - 1])
-                return fail(SNN_ERR_BAD_ARG, "presynaptic indices of a row must be strictly ascending");
-            if (weights[e] != weights[e])          // (the dense form cannot hold such an edge: the two forms refuse alike)
-                return fail(SNN_ERR_BAD_ARG, "stored edge " + std::to_string(e) + " (pre " + std::to_string(pre_index[e]) + ") carries a NaN weight");
-            post[e] = q;
-            ++t_ptr[pre_index[e] + 1];
-        }
-    }
-    // SELL-64: every slice (64 rows) is padded to its longest row
-    uint64_t entries = 0;
-    for (uint32_t sl = 0; sl < n_slices; ++sl) {
-        uint32_t width = 0;
-        for (uint32_t r = sl * 64; r < sl * 64 + 64; ++r) width = std::max(width, row_len[r]);
-        slice_ptr[sl] = (uint32_t)entries;
-        entries += (uint64_t)width * 64;
-        if (entries >= 0xFFFFFFFFull) return fail(SNN_ERR_DIM_MISMATCH, "sparse graph too large for 32-bit slots");
-    }
-    slice_ptr[n_slices] = (uint32_t)entries;
-    hvec<uint32_t> sell_pre(entries, SELL_PAD);
-    hvec<float> sell_w(entries, 0.0f);
-    for (uint32_t k = 0; k < n_rows; ++k) {
-        const uint32_t q = local(k);
-        const uint32_t base = slice_ptr[q >> 6] + (q & 63u);
-        for (uint64_t e = row_ptr[k]; e < row_ptr[k + 1]; ++e) {
-            const uint32_t slot = base + (uint32_t)(e - row_ptr[k]) * 64;
-            sell_pre[slot] = pre_index[e];
-            sell_w[slot] = weights[e];
-            edge_slot[e] = slot;
-        }
-    }
-    for (size_t p = 0; p < net->n_tot; ++p) t_ptr[p + 1] += t_ptr[p];
-    {
-        hvec<uint32_t> fill(t_ptr.begin(), t_ptr.end() - 1);
-        for (uint64_t e = 0; e < nnz; ++e) t_edge[fill[pre_index[e]]++] = (uint32_t)e;
-    }
-    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
-    TRY(end_run(net));
-    // everything of the new graph goes into locals first (device arrays, gather plan, step image, halo lists, cell list); the
-    // commit below only moves and swaps
-    dev_ptr<uint32_t> slice_ptr_d, pre_d, row_len_d, edge_slot_d, post_d, t_ptr_d, t_edge_d, plan_d, img_hdr_d, plan_win_d;
-    dev_ptr<float> w_d;
-    dev_ptr<uint4> img_rec_d;
-    auto up = [&](auto *dst, const void *src, size_t bytes) -> int {
-        HIP_TRY(snn_malloc(dst, std::max<size_t>(bytes, 256)), SNN_ERR_BUFFER_CREATE);
-        if (bytes) HIP_TRY(copy_sync(net, *dst, src, bytes, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        return SNN_OK;
-    };
-    TRY(up(&slice_ptr_d, slice_ptr.data(), slice_ptr.size() * 4));
-    TRY(up(&pre_d, sell_pre.data(), entries * 4));
-    TRY(up(&w_d, sell_w.data(), entries * 4));
-    TRY(up(&row_len_d, row_len.data(), row_len.size() * 4));
-    TRY(up(&edge_slot_d, edge_slot.data(), nnz * 4));
-    TRY(up(&post_d, post.data(), nnz * 4));
-    TRY(up(&t_ptr_d, t_ptr.data(), t_ptr.size() * 4));
-    TRY(up(&t_edge_d, t_edge.data(), nnz * 4));
-    HIP_TRY(snn_malloc(&plan_d, std::max<size_t>(entries * 4, 256)), SNN_ERR_BUFFER_CREATE);
-    uint64_t img_records = 0, img_staged_slices = 0;
-    {
-        // the step image's host-built half: slice headers with the window pieces, and the plan words that go with them
-        hvec<uint32_t> img_hdr, plan_win;
-        build_step_image_plan(net, slice_ptr, sell_pre, n_slices, img_hdr, plan_win, img_records, img_staged_slices);
-        TRY(up(&img_hdr_d, img_hdr.data(), img_hdr.size() * 4));
-        TRY(up(&plan_win_d, plan_win.data(), plan_win.size() * 4));
-        HIP_TRY(snn_malloc(&img_rec_d, (size_t)img_records * 16 + 4096), SNN_ERR_BUFFER_CREATE);    // (+ a wavefront's load of slack)
-    }
-    if (n_slices) {
-        SellGraph g = csr_graph(net);                 // (the handle's geometry, the new arrays)
-        g.slice_ptr = slice_ptr_d; g.pre = pre_d; g.w = w_d; g.row_len = row_len_d;
-        g.edge_slot = edge_slot_d; g.edge_post = post_d; g.t_ptr = t_ptr_d; g.t_edge = t_edge_d; g.plan = plan_d;
-        hipLaunchKernelGGL(k_csr_plan, dim3((n_slices * 64 + 255) / 256), dim3(256), 0, net->stream, g,
-                           plan_d, (const uint32_t *)nullptr, net->nn, PLAN_CODE);
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-    }
-    // the new rows decide what is read from the other shards, and which spike-train cells this rank reads at all
-    hvec<hvec<uint32_t>> halo_need(net->n_shards), halo_send(net->n_shards);
-    halo_needs_from_rows(net, pre_index, nnz, halo_need);
-    const bool list_cells = net->sharded && net->n_shards > 1 && net->nc;
-    hvec<uint32_t> cells;
-    dev_ptr<uint32_t> cells_d;
-    if (list_cells) {
-        hvec<uint8_t> seen(net->nc, 0);
-        for (uint64_t e = 0; e < nnz; ++e)
-            if (pre_index[e] >= net->nn) seen[pre_index[e] - net->nn] = 1;
-        for (uint32_t s = 0; s < net->nc; ++s)
-            if (seen[s]) cells.push_back(s);
-        TRY(upload_table(net, &cells_d, cells));
-    }
-    // ---- the commit ----
-    net->csr_ptr = std::move(slice_ptr_d); net->csr_pre = std::move(pre_d); net->csr_w = std::move(w_d);
-    net->csr_row_len = std::move(row_len_d); net->csr_edge_slot = std::move(edge_slot_d); net->csr_post = std::move(post_d);
-    net->csr_t_ptr = std::move(t_ptr_d); net->csr_t_edge = std::move(t_edge_d); net->csr_plan = std::move(plan_d);
-    net->csr_img_hdr = std::move(img_hdr_d); net->csr_plan_win = std::move(plan_win_d); net->csr_img_rec = std::move(img_rec_d);
-    net->img_records = img_records; net->img_staged_slices = img_staged_slices;
-    net->img_stale = net->img_stale_direct = true;
-    if (keep) { keep->trace = std::move(net->trace); keep->pending = std::move(net->pending); keep->edge_counter = std::move(net->edge_counter); }
-    net->trace = nullptr;                                        // traces belong to the replaced edges
-    net->pending = nullptr; net->edge_counter = nullptr;         // ... and so do dw and the counters of its connections
-    net->cross_checked = false;
-    net->nnz = nnz;
-    net->sell_entries = entries;
-    net->edge_slot_host.swap(edge_slot);
-    if (net->sharded && net->n_shards > 1) { net->sell_pre_host.swap(sell_pre); net->slice_ptr_host.swap(slice_ptr); }
-    else { net->sell_pre_host.clear(); net->slice_ptr_host.clear(); }
-    net->cache.counts_dirty = true;
-    net->halo_need.swap(halo_need); net->halo_send.swap(halo_send);
-    net->halo_committed = false; net->x_dirty = true;
-    if (list_cells) {
-        net->cell_list_host.swap(cells);
-        net->cell_list_dev = std::move(cells_d);
-        net->n_cells_listed = (uint32_t)net->cell_list_host.size();
-        net->cache.view_dirty = true;
-    }
-    // a reward-modulated handle keeps modulating: zeroed traces for the new edges, sized by the committed graph (see above)
-    if (net->any_modulation || net->any_conn_kind) TRY(ensure_traces(net));
-    if (net->any_conn_kind) TRY(ensure_pending(net));
-    return SNN_OK;
-}
-
 int snn_set_graph_csr(snn_network_t *net, const uint64_t *row_ptr, const uint32_t *pre_index, const float *weights,
                       uint64_t nnz) ABI_TRY
 {
@@ -1005,7 +373,15 @@ int snn_set_graph_csr(snn_network_t *net, const uint64_t *row_ptr, const uint32_
     }
 }
 ABI_CATCH
-
+int snn_graph_csr_nnz(snn_network_t *net, uint64_t *nnz) ABI_TRY
+{
+    if (!net || !nnz) return fail(SNN_ERR_BAD_ARG, "null argument");
+    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
+    if (!net->csr) return fail(SNN_ERR_BAD_STATE, "handle holds a dense graph");
+    *nnz = net->nnz;
+    return SNN_OK;
+}
+ABI_CATCH
 int snn_get_graph_csr(snn_network_t *net, float *weights, uint64_t nnz) ABI_TRY
 {
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
@@ -1019,16 +395,6 @@ int snn_get_graph_csr(snn_network_t *net, float *weights, uint64_t nnz) ABI_TRY
     hvec<float> sell((size_t)net->sell_entries);
     HIP_TRY(copy_sync(net, sell.data(), net->csr_w, sell.size() * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
     for (uint64_t e = 0; e < nnz; ++e) weights[e] = sell[net->edge_slot_host[e]];
-    return SNN_OK;
-}
-ABI_CATCH
-
-int snn_graph_csr_nnz(snn_network_t *net, uint64_t *nnz) ABI_TRY
-{
-    if (!net || !nnz) return fail(SNN_ERR_BAD_ARG, "null argument");
-    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
-    if (!net->csr) return fail(SNN_ERR_BAD_STATE, "handle holds a dense graph");
-    *nnz = net->nnz;
     return SNN_OK;
 }
 ABI_CATCH
@@ -1058,316 +424,11 @@ int snn_get_graph_csr_structure(snn_network_t *net, uint64_t *row_ptr, uint32_t 
     return SNN_OK;
 }
 ABI_CATCH
-
-// snn_connect_by_rules_csr (specs == nullptr: every record plain) and snn_connect_by_specs_csr (records == nullptr): one body
-static int connect_csr(snn_network_t *net, const snn_connect_record *records, const snn_connect_spec *specs, uint32_t n_records)
-{
-    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
-    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
-    if (!net->csr) return fail(SNN_ERR_BAD_STATE, "handle holds a dense graph: connect it with snn_connect_by_rule");
-    if (net->block_mode) return fail(SNN_ERR_BAD_STATE, "connecting by rule does not cover shards by lattice (range-set ownership): not covered");
-    if (n_records == 0) return SNN_OK;
-    if (!records && !specs) return fail(SNN_ERR_BAD_ARG, "records is null");
-    hvec<std::pair<const LatticeInfo *, const LatticeInfo *>> ends(n_records);
-    hvec<ConnectSpecExt> exts(n_records);
-    for (uint32_t k = 0; k < n_records; ++k) {
-        const std::string where = "record " + std::to_string(k) + ": ";
-        if (specs) {
-            TRY(connect_spec_check(net, where, specs[k], &ends[k].first, &ends[k].second, &exts[k]));
-            continue;
-        }
-        const snn_connect_record &r = records[k];
-        TRY(connect_check(net, where, r.pre_id, r.post_id, r.rule, r.probability, r.weight_rule, r.w_lo, r.w_hi, &ends[k].first, &ends[k].second, CONNECT_RULE_WEIGHTS));
-    }
-    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
-    TRY(end_run(net));                     // a deferred update belongs to the weights the merge is about to read
-    const uint32_t n = net->n_loc, scan_blocks = (n + 255u) / 256u;
-    // two sets of working CSR (the merge of a record reads one and writes the other), the row lengths and the scan's words: all
-    // locals, freed on every exit
-    dev_ptr<uint32_t> ptr[2], pre[2], len_d;
-    dev_ptr<float> w[2];
-    dev_ptr<unsigned long long> sums_d;              // [scan_blocks] block sums, then [1] the total
-    auto sized = [&](auto *dst, size_t bytes) -> int {
-        HIP_TRY(snn_malloc(dst, std::max<size_t>(bytes, 256)), SNN_ERR_BUFFER_CREATE);
-        return SNN_OK;
-    };
-    for (int s = 0; s < 2; ++s) TRY(sized(&ptr[s], ((size_t)n + 1) * 4));
-    TRY(sized(&len_d, (size_t)n * 4));
-    TRY(sized(&sums_d, ((size_t)scan_blocks + 1) * 8));
-    unsigned long long *total_d = sums_d.get() + scan_blocks;
-    // lengths -> ptr (n + 1 offsets), the 64-bit total read back
-    auto scan = [&](const uint32_t *len, uint32_t *out, uint64_t *total) -> int {
-        *total = 0;
-        if (n == 0) return hipMemsetAsync(out, 0, 4, net->stream) == hipSuccess ? SNN_OK : fail(SNN_ERR_BUFFER_WRITE, "hipMemsetAsync failed");
-        hipLaunchKernelGGL(k_connect_scan_local, dim3(scan_blocks), dim3(256), 0, net->stream, len, n, out, sums_d.get());
-        hipLaunchKernelGGL(k_connect_scan_sums, dim3(1), dim3(256), 0, net->stream, sums_d.get(), scan_blocks, total_d);
-        hipLaunchKernelGGL(k_connect_scan_add, dim3(scan_blocks), dim3(256), 0, net->stream, out, n, (const unsigned long long *)sums_d.get(),
-                           (const unsigned long long *)total_d);
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        unsigned long long t = 0;
-        HIP_TRY(copy_sync(net, &t, total_d, 8, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-        *total = t;
-        return SNN_OK;
-    };
-    // ---- the current graph, from SELL-64 (weights as plasticity left them) ----
-    int cur = 0;
-    uint64_t nnz = 0;
-    if (net->csr_ptr && n) {
-        TRY(scan(net->csr_row_len, ptr[cur], &nnz));
-        if (nnz != net->nnz) return fail(SNN_ERR_BAD_STATE, "stored row lengths do not add up to the stored edge count");
-        TRY(sized(&pre[cur], nnz * 4));
-        TRY(sized(&w[cur], nnz * 4));
-        hipLaunchKernelGGL(k_connect_csr_export, dim3(scan_blocks), dim3(256), 0, net->stream, (const uint32_t *)net->csr_ptr,
-                           (const uint32_t *)net->csr_pre, (const float *)net->csr_w, (const uint32_t *)net->csr_row_len,
-                           (const uint32_t *)ptr[cur], n, pre[cur].get(), w[cur].get());
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-    } else {
-        HIP_TRY(hipMemsetAsync(ptr[cur], 0, ((size_t)n + 1) * 4, net->stream), SNN_ERR_BUFFER_WRITE);
-        TRY(sized(&pre[cur], 0));
-        TRY(sized(&w[cur], 0));
-    }
-    // ---- record by record: count, scan, check the total, fill, swap ----
-    for (uint32_t k = 0; k < n_records; ++k) {
-        const snn_connect_record &r = specs ? specs[k].record : records[k];
-        const LatticeInfo *lp = ends[k].first, *lq = ends[k].second;
-        // the block's rows this handle owns, as local rows (the dense form: its columns)
-        const uint32_t c_begin = std::max(lq->first, net->q0), c_end = std::min(lq->first + lq->count, net->q0 + n);
-        if (!n || c_begin >= c_end) continue;          // (an empty pre lattice still clears nothing: the block has no pair)
-        if (!lp->count) continue;
-        ConnectCsrArgs a{};
-        a.c.col0 = c_begin - net->q0; a.c.n_cols = c_end - c_begin; a.c.post_i0 = c_begin - lq->first;
-        a.c.post_cols = lq->cols; a.c.post_count = lq->count;
-        a.c.pre_first = lp->first; a.c.pre_count = lp->count; a.c.pre_rows = lp->rows; a.c.pre_cols = lp->cols;
-        a.c.extent = r.extent; a.c.probability = r.probability; a.c.edge_seed = r.edge_seed; a.c.weight_seed = r.weight_seed;
-        a.c.w_lo = r.w_lo; a.c.w_hi = r.w_hi;
-        a.n_rows = n;
-        a.window = connect_window_extent(r.rule, r.extent, std::max(std::max(lp->rows, lp->cols), std::max(lq->rows, lq->cols)));
-        a.old_ptr = ptr[cur]; a.old_pre = pre[cur]; a.old_w = w[cur];
-        a.new_len = len_d;
-        const bool thin = r.probability < 1.0f, self = r.self_edges != 0, wrap = exts[k].period_r || exts[k].period_c;
-        const bool plain = connect_spec_is_plain((int)r.rule, (int)r.weight_rule, wrap);
-        dev_ptr<float> table_d;                        // (read by both passes; freed after the wait that ends this record)
-        if (specs) TRY(connect_spec_upload(net, specs[k], &exts[k], &table_d));
-        const dim3 grid(std::min<uint32_t>((n + 3u) / 4u, 16384u));
-        if (plain)
-            hipLaunchKernelGGL(connect_csr_kernel<false>((int)r.rule, (int)r.weight_rule, thin, self), grid, dim3(256), 0, net->stream, a);
-        else
-            hipLaunchKernelGGL(connect_csr_spec_kernel<false>((int)r.rule, (int)r.weight_rule, wrap, thin, self), grid, dim3(256), 0, net->stream,
-                               ConnectCsrSpecArgs{a, exts[k]});
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        uint64_t total = 0;
-        TRY(scan(len_d, ptr[cur ^ 1], &total));
-        if (total >= 0xFFFFFFFFull)
-            return fail(SNN_ERR_DIM_MISMATCH, "record " + std::to_string(k) + ": the graph would hold " + std::to_string(total) +
-                                                  " stored synapses, more than 2^32-2 per handle");
-        TRY(sized(&pre[cur ^ 1], total * 4));
-        TRY(sized(&w[cur ^ 1], total * 4));
-        a.new_ptr = ptr[cur ^ 1]; a.new_pre = pre[cur ^ 1]; a.new_w = w[cur ^ 1];
-        if (plain)
-            hipLaunchKernelGGL(connect_csr_kernel<true>((int)r.rule, (int)r.weight_rule, thin, self), grid, dim3(256), 0, net->stream, a);
-        else
-            hipLaunchKernelGGL(connect_csr_spec_kernel<true>((int)r.rule, (int)r.weight_rule, wrap, thin, self), grid, dim3(256), 0, net->stream,
-                               ConnectCsrSpecArgs{a, exts[k]});
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);      // (the set just read is freed when it is next sized)
-        cur ^= 1;
-        nnz = total;
-    }
-    // ---- one download, then the host builder of snn_set_graph_csr: all or nothing from here as before here ----
-    hvec<uint32_t> ptr32((size_t)n + 1), pre_h((size_t)nnz);
-    hvec<float> w_h((size_t)nnz);
-    HIP_TRY(copy_sync(net, ptr32.data(), ptr[cur], ptr32.size() * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-    if (nnz) {
-        HIP_TRY(copy_sync(net, pre_h.data(), pre[cur], nnz * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-        HIP_TRY(copy_sync(net, w_h.data(), w[cur], nnz * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-    }
-    for (int s = 0; s < 2; ++s) { ptr[s].reset(); pre[s].reset(); w[s].reset(); }      // (the commit peaks at old graph + new graph)
-    len_d.reset(); sums_d.reset();
-    hvec<uint64_t> ptr64(ptr32.begin(), ptr32.end());
-    hvec<uint32_t>().swap(ptr32);
-    uint32_t no_pre = 0;
-    float no_w = 0.0f;
-    return set_graph_csr_impl(net, ptr64.data(), nnz ? pre_h.data() : &no_pre, nnz ? w_h.data() : &no_w, nnz);
-}
-
 int snn_connect_by_rules_csr(snn_network_t *net, const snn_connect_record *records, uint32_t n_records) ABI_TRY
-{
-    return connect_csr(net, records, nullptr, n_records);
-}
+{ return connect_csr(net, records, nullptr, n_records); }
 ABI_CATCH
-
 int snn_connect_by_specs_csr(snn_network_t *net, const snn_connect_spec *specs, uint32_t n_specs) ABI_TRY
-{
-    return connect_csr(net, nullptr, specs, n_specs);
-}
-ABI_CATCH
-
-// edit_weight(pre, post, Option<f32>) on a sparse handle, structure included (graph/mod.rs:42-72, 204-213): the sorted edit list
-// merged into the stored rows on the device (snn_kernels_graph_merge_csr.hpp), committed as connect_csr commits.  Nothing of the
-// handle is written before the commit -- or, when no pair inserts or removes, before the in-place store of snn_graph_csr_edit.
-int snn_graph_csr_edit_structure(snn_network_t *net, const uint32_t *pre, const uint32_t *post, const float *weights,
-                                 const uint8_t *connected, size_t n) ABI_TRY
-{
-    TRY(graph_csr_begin(net));
-    if (n == 0) return SNN_OK;
-    if (!pre || !post || !weights || !connected) return fail(SNN_ERR_BAD_ARG, "null pointer with n > 0");
-    // every pair is checked before anything is written: a refused call leaves the graph as it was
-    for (size_t k = 0; k < n; ++k) {
-        if (pre[k] >= net->n_tot || post[k] - net->q0 >= net->n_loc) return graph_pair_check(net, "pair " + std::to_string(k), pre[k], post[k]);
-        if (connected[k] && weights[k] != weights[k])
-            return fail(SNN_ERR_BAD_ARG, graph_csr_pair(k, pre[k], post[k]) + ": a connected edge carries a NaN weight; NaN is the absent-edge "
-                                         "sentinel of the dense form, which the sparse form refuses alike (graph/mod.rs:204-213).  Nothing of "
-                                         "this call was applied");
-    }
-    // "as if one after another": of a pair listed more than once the last occurrence decides, whatever the earlier ones asked for;
-    // the list sorted by (post, pre) is the order the rows of the merge read it in
-    hvec<uint64_t> order;
-    const size_t kept = graph_merge_order(pre, post, n, order);
-    if (kept >= 0xFFFFFFFFull) return fail(SNN_ERR_DIM_MISMATCH, "more than 2^32-2 distinct pairs in one call");
-    const uint32_t m = (uint32_t)kept, rows = net->n_loc;
-    const size_t hop = std::min(kept, GRAPH_PAIRS_HOP);
-    hvec<uint32_t> pre_h(hop), post_h(hop);
-    hvec<float> value_h(hop);
-    hvec<uint8_t> on_h(hop);
-    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
-    TRY(end_run(net));                     // a deferred update belongs to the weights the merge is about to read
-    const bool timing = getenv("SNN_DEBUG_EDIT_TIMING") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(now() - t).count(); };
-    const auto t_begin = now();
-    const uint32_t scan_edits = (m + 255u) / 256u, scan_rows = (rows + 255u) / 256u;
-    dev_ptr<uint32_t> pre_d, post_d, slot_d, ins_d, rem_d, len_d, ptr_d, new_pre_d, src_d;
-    dev_ptr<uint8_t> on_d;
-    dev_ptr<float> value_d, new_w_d;
-    dev_ptr<unsigned long long> sums_d;              // [blocks] block sums of a scan, then [1] its total
-    auto sized = [&](auto *dst, size_t bytes) -> int {
-        HIP_TRY(snn_malloc(dst, std::max<size_t>(bytes, 256)), SNN_ERR_BUFFER_CREATE);
-        return SNN_OK;
-    };
-    TRY(sized(&pre_d, kept * 4));
-    TRY(sized(&post_d, kept * 4));
-    TRY(sized(&value_d, kept * 4));
-    TRY(sized(&on_d, kept));
-    TRY(sized(&slot_d, kept * 4));
-    TRY(sized(&ins_d, (kept + 1) * 4));
-    TRY(sized(&rem_d, (kept + 1) * 4));
-    TRY(sized(&sums_d, ((size_t)std::max(scan_edits, scan_rows) + 1) * 8));
-    if (net->opt.pinned_copies && !net->copy_stage)           // (the staging buffer of copy_sync: allocated before the first write)
-        HIP_TRY(host_malloc(&net->copy_stage, (size_t)8 << 20, hipHostMallocDefault), SNN_ERR_BUFFER_CREATE);
-    // ---- the resolve pass: read only.  The sorted list goes up in hops; every pair finds its entry ----
-    for (size_t k = 0; k < kept; k += hop) {
-        const uint32_t h = (uint32_t)std::min(hop, kept - k);
-        for (uint32_t j = 0; j < h; ++j) {
-            const size_t src = (size_t)order[k + j];
-            pre_h[j] = pre[src]; post_h[j] = post[src]; value_h[j] = weights[src]; on_h[j] = connected[src] ? 1 : 0;
-        }
-        HIP_TRY(copy_sync(net, pre_d.get() + k, pre_h.data(), (size_t)h * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        HIP_TRY(copy_sync(net, post_d.get() + k, post_h.data(), (size_t)h * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        HIP_TRY(copy_sync(net, value_d.get() + k, value_h.data(), (size_t)h * 4, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        HIP_TRY(copy_sync(net, on_d.get() + k, on_h.data(), h, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
-        if (net->csr_ptr)
-            hipLaunchKernelGGL(k_graph_csr_find, dim3((h + 255u) / 256u), dim3(256), 0, net->stream, (const uint32_t *)net->csr_ptr,
-                               (const uint32_t *)net->csr_pre, (const float *)net->csr_w, (const uint32_t *)net->csr_row_len, net->q0,
-                               (const uint32_t *)(pre_d.get() + k), (const uint32_t *)(post_d.get() + k), h, slot_d.get() + k, (float *)nullptr,
-                               (uint8_t *)nullptr, (const uint8_t *)nullptr, 0ull, (unsigned long long *)nullptr);
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-    }
-    if (!net->csr_ptr)                     // no graph set yet: the empty one, no pair has an entry (GRAPH_CSR_NONE is all ones)
-        HIP_TRY(hipMemsetAsync(slot_d, 0xFF, kept * 4, net->stream), SNN_ERR_BUFFER_WRITE);
-    hipLaunchKernelGGL(k_graph_merge_flags, dim3(scan_edits), dim3(256), 0, net->stream, (const uint32_t *)slot_d, (const uint8_t *)on_d, m,
-                       ins_d.get(), rem_d.get());
-    HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-    // flags or lengths -> count + 1 offsets, in place (every thread reads its word before the block's first write), the total read back
-    auto scan = [&](uint32_t *words, uint32_t count, uint64_t *total) -> int {
-        const uint32_t blocks = (count + 255u) / 256u;
-        unsigned long long *total_d = sums_d.get() + blocks;
-        hipLaunchKernelGGL(k_connect_scan_local, dim3(blocks), dim3(256), 0, net->stream, (const uint32_t *)words, count, words, sums_d.get());
-        hipLaunchKernelGGL(k_connect_scan_sums, dim3(1), dim3(256), 0, net->stream, sums_d.get(), blocks, total_d);
-        hipLaunchKernelGGL(k_connect_scan_add, dim3(blocks), dim3(256), 0, net->stream, words, count, (const unsigned long long *)sums_d.get(),
-                           (const unsigned long long *)total_d);
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        unsigned long long t = 0;
-        HIP_TRY(copy_sync(net, &t, total_d, 8, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-        *total = t;
-        return SNN_OK;
-    };
-    uint64_t inserts = 0, removes = 0;
-    TRY(scan(ins_d, m, &inserts));
-    TRY(scan(rem_d, m, &removes));
-    if (inserts == 0 && removes == 0) {
-        // ---- nothing inserts, nothing removes: the write pass of snn_graph_csr_edit, in place ("stay absent" has no entry and is
-        // skipped; no pair is listed twice) ----
-        if (!net->csr_ptr) return SNN_OK;
-        net->cross_checked = false;
-        net->img_stale = net->img_stale_direct = true;             // the step image's records are packed again before the next image step
-        hipLaunchKernelGGL(k_graph_csr_store, dim3(scan_edits), dim3(256), 0, net->stream, net->csr_w.get(), net->trace.get(),
-                           net->pending.get(), net->edge_counter.get(), (const uint32_t *)slot_d, (const unsigned long long *)nullptr,
-                           (const float *)value_d, m);
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
-        return SNN_OK;
-    }
-    // ---- the structural path: lengths, offsets, the 2^32-2 check, then every entry placed on its own ----
-    TRY(sized(&len_d, ((size_t)rows + 1) * 4));
-    GraphMergeArgs a{};
-    if (net->csr_ptr) { a.slice_ptr = net->csr_ptr; a.sell_pre = net->csr_pre; a.row_len = net->csr_row_len; a.sell_w = net->csr_w; }
-    a.edit_pre = pre_d; a.edit_post = post_d; a.ins_before = ins_d; a.rem_before = rem_d; a.edit_w = value_d;
-    a.n_edits = m; a.n_rows = rows; a.q0 = net->q0;
-    a.new_len = len_d;
-    hipLaunchKernelGGL(k_graph_merge_count, dim3(scan_rows), dim3(256), 0, net->stream, a);
-    HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-    uint64_t nnz = 0;
-    TRY(scan(len_d, rows, &nnz));
-    if (nnz >= 0xFFFFFFFFull)
-        return fail(SNN_ERR_DIM_MISMATCH, "the graph would hold " + std::to_string(nnz) + " stored synapses, more than 2^32-2 per handle");
-    if (nnz != net->nnz + inserts - removes) return fail(SNN_ERR_BAD_STATE, "the merged row lengths do not add up to stored + inserted - removed");
-    TRY(sized(&new_pre_d, nnz * 4));
-    TRY(sized(&new_w_d, nnz * 4));
-    TRY(sized(&src_d, nnz * 4));
-    a.new_ptr = len_d; a.new_pre = new_pre_d; a.new_w = new_w_d; a.new_src = src_d;
-    hipLaunchKernelGGL(k_graph_merge_fill, dim3(std::min<uint32_t>((rows + 3u) / 4u, 16384u)), dim3(256), 0, net->stream, a);
-    HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-    HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
-    const double ms_merge = ms_since(t_begin);
-    // ---- one download, then the host builder of snn_set_graph_csr: all or nothing from here as before here ----
-    const auto t_download = now();
-    hvec<uint32_t> ptr32((size_t)rows + 1), new_pre_h((size_t)nnz);
-    hvec<float> new_w_h((size_t)nnz);
-    HIP_TRY(copy_sync(net, ptr32.data(), len_d, ptr32.size() * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-    if (nnz) {
-        HIP_TRY(copy_sync(net, new_pre_h.data(), new_pre_d, nnz * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-        HIP_TRY(copy_sync(net, new_w_h.data(), new_w_d, nnz * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
-    }
-    // (the commit peaks at old graph + new graph: everything but the source of every new edge goes now)
-    pre_d.reset(); post_d.reset(); value_d.reset(); on_d.reset(); slot_d.reset(); ins_d.reset(); rem_d.reset(); len_d.reset();
-    new_pre_d.reset(); new_w_d.reset(); sums_d.reset();
-    hvec<uint64_t> ptr64(ptr32.begin(), ptr32.end());
-    hvec<uint32_t>().swap(ptr32);
-    const double ms_download = ms_since(t_download);
-    const auto t_commit = now();
-    uint32_t no_pre = 0;
-    float no_w = 0.0f;
-    CsrEdgePlanes old;
-    TRY(set_graph_csr_impl(net, ptr64.data(), nnz ? new_pre_h.data() : &no_pre, nnz ? new_w_h.data() : &no_w, nnz, &old));
-    const double ms_commit = ms_since(t_commit);
-    // ---- per-edge state: the planes the handle carried, from the old entry of every kept edge to its new one (a handle with
-    // modulation or connection kinds has zeroed planes again by now; planes set without either are allocated here) ----
-    if (old.trace) TRY(ensure_traces(net));
-    if (old.pending) TRY(ensure_pending(net));
-    if (nnz && (old.trace || old.pending)) {
-        hipLaunchKernelGGL(k_graph_merge_carry, dim3(((uint32_t)nnz + 255u) / 256u), dim3(256), 0, net->stream, (const uint32_t *)src_d,
-                           (const uint32_t *)net->csr_edge_slot, (uint32_t)nnz, (const float *)old.trace, old.trace ? net->trace.get() : nullptr,
-                           (const float *)old.pending, old.pending ? net->pending.get() : nullptr, (const float *)old.edge_counter,
-                           old.edge_counter ? net->edge_counter.get() : nullptr);
-        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
-        HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
-    }
-    if (timing)
-        fprintf(stderr, "[snn] edit_structure: %u edits (%llu inserts, %llu removes), %llu edges: resolve+merge %.3f ms, download %.3f ms, "
-                        "host builder %.3f ms, carry %.3f ms\n", m, (unsigned long long)inserts, (unsigned long long)removes,
-                (unsigned long long)nnz, ms_merge, ms_download, ms_commit, ms_since(t_commit) - ms_commit);
-    return SNN_OK;
-}
+{ return connect_csr(net, nullptr, specs, n_specs); }
 ABI_CATCH
 
 int snn_set_synapses(snn_network_t *net, int electrical_synapse, int chemical_synapse) ABI_TRY

@@ -590,14 +590,15 @@ inline hipError_t snn_malloc(dev_ptr<T> *out, size_t bytes)
 // thread.  What it excludes: the runtime's own staging of pageable copies, whose host-side half runs on a runtime thread
 // (campaign E, profiles/r05/README.md: under 24 worker processes on 16 cores one execution ended with two words of the oracle's
 // memory overwritten by what looks like a spike-raster word, another with a voltage history that did not match its own final state).
+constexpr size_t STAGE = (size_t)8 << 20;             // the page-locked buffer of a handle, allocated with the first copy that needs it
+inline hipError_t copy_stage_alloc(snn_network *net)
+{
+    return net->copy_stage ? hipSuccess : host_malloc(&net->copy_stage, STAGE, hipHostMallocDefault);
+}
 inline hipError_t copy_sync(snn_network *net, void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
 {
     if (net->opt.pinned_copies && bytes && (kind == hipMemcpyDeviceToHost || kind == hipMemcpyHostToDevice)) {
-        constexpr size_t STAGE = (size_t)8 << 20;
-        if (!net->copy_stage) {
-            const hipError_t e = host_malloc(&net->copy_stage, STAGE, hipHostMallocDefault);
-            if (e != hipSuccess) return e;
-        }
+        if (const hipError_t e = copy_stage_alloc(net); e != hipSuccess) return e;
         for (size_t off = 0; off < bytes; off += STAGE) {
             const size_t n = std::min(STAGE, bytes - off);
             if (kind == hipMemcpyHostToDevice) memcpy(net->copy_stage, static_cast<const char *>(src) + off, n);
@@ -619,12 +620,8 @@ inline hipError_t copy2d_sync(snn_network *net, void *dst, size_t dpitch, const 
                               hipMemcpyKind kind)
 {
     if (net->opt.pinned_copies >= 2 && width && height && (kind == hipMemcpyDeviceToHost || kind == hipMemcpyHostToDevice)) {
-        constexpr size_t STAGE = (size_t)8 << 20;
         if (width > STAGE) return hipErrorInvalidValue;
-        if (!net->copy_stage) {
-            const hipError_t e = host_malloc(&net->copy_stage, STAGE, hipHostMallocDefault);
-            if (e != hipSuccess) return e;
-        }
+        if (const hipError_t e = copy_stage_alloc(net); e != hipSuccess) return e;
         const size_t rows_per_hop = std::max<size_t>(1, STAGE / width);
         char *stage = static_cast<char *>(net->copy_stage);
         for (size_t r = 0; r < height; r += rows_per_hop) {

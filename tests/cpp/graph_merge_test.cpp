@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "snn_graph_merge.hpp"
+#include "snn_graph_pairs.hpp"
 
 using namespace snn;
 
@@ -57,7 +58,7 @@ static bool merge_by_formulas(const Rows &rows, const std::vector<Edit> &edits, 
     std::vector<uint32_t> call_pre(edits.size()), call_post(edits.size());
     for (size_t k = 0; k < edits.size(); ++k) { call_pre[k] = edits[k].pre; call_post[k] = edits[k].post; }
     std::vector<uint64_t> order;
-    const uint32_t m = (uint32_t)graph_merge_order(call_pre.data(), call_post.data(), edits.size(), order);
+    const uint32_t m = (uint32_t)graph_pairs_last_wins(call_pre.data(), call_post.data(), edits.size(), GRAPH_KEY_POST_PRE, order);
     std::vector<uint32_t> e_pre(m), e_post(m), slot(m), ins(m + 1, 0), rem(m + 1, 0);
     std::vector<float> e_w(m);
     for (uint32_t t = 0; t < m; ++t) {
