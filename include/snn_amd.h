@@ -658,6 +658,32 @@ int snn_set_firing_times(snn_network_t *net, uint32_t id, const uint32_t *cell_p
 int snn_set_graph_history(snn_network_t *net, uint32_t id, int enable);
 int snn_get_graph_history(snn_network_t *net, uint32_t id, float *dst, size_t steps);
 
+/* Edge-weight history: the weights of a caller-chosen list of (pre, post) pairs per recorded step, on dense AND sparse unsharded
+ * handles, O(pairs) per step.  It is the connecting graph's history (update_connecting_graph_history; recorded after the step's
+ * weight updates, LatticeNetwork::iterate*, neuron/mod.rs:2463-2465, 2521-2523, 2578-2580, 5045-5047) and, where the
+ * [n][n] snapshot of snn_set_graph_history cannot exist, a lattice's own (graph/mod.rs:278-280).
+ * snn_set_edge_history installs the list and replaces any earlier one; n == 0 switches the recorder off and frees its buffers.
+ * Indices are the interleaved global indices of snn_graph_lookup (pre < n_tot: spike-train cells are valid; post < n_neurons).
+ * when[k] is 1 (AFTER the step's weight updates) or 2 (BEFORE them), as snn_set_graph_history's `enable`; when == NULL: 1 for
+ * every pair.  A pair may appear more than once: each occurrence is a column of its own.  Every pair is checked before anything
+ * changes (SNN_ERR_BAD_ARG naming "pair k (pre .., post ..)"); a refused call leaves the installed list and its record as they
+ * were.  Installing, replacing or removing a list restarts the record (all recorded rows cover the same steps); the record
+ * follows snn_set_history_stride, snn_reset_history and snn_history_steps.  Shard handles of any kind and handles that are not
+ * finalized: SNN_ERR_BAD_STATE.
+ * Pairs are identities, not storage slots: on a sparse handle each pair resolves to its stored edge or to "absent" when the list
+ * is installed, and again after every call that commits a structure (snn_set_graph_csr, snn_connect_by_rules_csr,
+ * snn_connect_by_specs_csr, an inserting or removing snn_graph_csr_edit_structure); the record goes on across the commit -- a pair
+ * whose edge was removed reads absent from then on, one that was connected reads its weight.  Weight-only edits show in the next
+ * recorded row.  A sparse handle without a graph records "absent" everywhere.  While a list is installed the weight updates of a
+ * step happen inside that step (no deferred STDP / R-STDP, no 24-bit image of W, no one-launch run), as with snn_set_graph_history.
+ * snn_get_edge_history: [steps][n] in the caller's pair order; weights holds the weight, 0.0f where the pair was absent at that
+ * step; connected (may be NULL) 1 / 0, so that Some(0.0) and None stay apart as in snn_graph_lookup.  steps must equal
+ * snn_history_steps (SNN_ERR_DIM_MISMATCH); no list installed: SNN_ERR_BAD_STATE.  snn_edge_history_count: n of the installed
+ * list, 0 without one.  Per recorded step and pair the device reads 12 B and writes 4 B (k_edge_history). */
+int snn_set_edge_history(snn_network_t *net, const uint32_t *pre, const uint32_t *post, const uint8_t *when, size_t n);
+int snn_get_edge_history(snn_network_t *net, float *weights, uint8_t *connected, size_t steps);
+int snn_edge_history_count(const snn_network_t *net, uint64_t *n);
+
 /* Strided capture: store the history rows (voltage, raster, reduced rows) of every `every`-th step only -- steps
  * 0, every, 2*every, ... counted from the last (re)start of the record; 1 = every step (the reference's
  * behaviour).  Changing the stride restarts the record.  Spike totals (below) always count every step. */

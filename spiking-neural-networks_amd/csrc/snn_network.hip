@@ -3,12 +3,14 @@
 // attribute registry), snn_network_step.hpp the kernel launches and the step loop (snn_dispatch.hpp: which template
 // instantiation a launch takes), snn_network_exchange.hpp the halo exchange between shards, snn_network_verify.hpp the "verify"
 // self-check of snn_run, snn_network_graph.hpp the bodies of the graph calls (graph setters, connect by rule, the Graph trait,
-// structural edits) and what they share -- their definitions here only pass the arguments on --, snn_kernels_*.hpp the kernels.
+// structural edits) and what they share -- their definitions here only pass the arguments on --, snn_network_edge_history.hpp the
+// edge-weight recorder's list, snn_kernels_*.hpp the kernels.
 #include "snn_network_state.hpp"
 #include "snn_network_step.hpp"
 #include "snn_network_exchange.hpp"
 #include "snn_network_verify.hpp"
 #include "snn_network_graph.hpp"
+#include "snn_network_edge_history.hpp"
 
 // ================================================================================================
 // C ABI
@@ -920,6 +922,20 @@ int snn_get_graph_history(snn_network_t *net, uint32_t id, float *dst, size_t st
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
     TRY(end_run(net));
     HIP_TRY(copy_sync(net, dst, net->whist[l->slot], steps * (size_t)l->count * l->count * 4, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+    return SNN_OK;
+}
+ABI_CATCH
+
+int snn_set_edge_history(snn_network_t *net, const uint32_t *pre, const uint32_t *post, const uint8_t *when, size_t n) ABI_TRY
+{ return set_edge_history(net, pre, post, when, n); }
+ABI_CATCH
+int snn_get_edge_history(snn_network_t *net, float *weights, uint8_t *connected, size_t steps) ABI_TRY
+{ return get_edge_history(net, weights, connected, steps); }
+ABI_CATCH
+int snn_edge_history_count(const snn_network_t *net, uint64_t *n) ABI_TRY
+{
+    if (!net || !n) return fail(SNN_ERR_BAD_ARG, "null argument");
+    *n = net->eh_slot.size();
     return SNN_OK;
 }
 ABI_CATCH

@@ -507,6 +507,7 @@ int graph_csr_edit(snn_network *net, const uint32_t *pre, const uint32_t *post, 
 }
 
 int ensure_traces(snn_network *net), ensure_pending(snn_network *net);       // (with the plasticity calls, in snn_network.hip)
+int edge_history_resolve(snn_network *net);                                  // (snn_network_edge_history.hpp)
 
 // All or nothing: a failed call leaves the previous graph in place, intact -- except that the traces / dw / counters of a handle
 // with modulation or connection kinds are sized by the new graph and allocated after the commit: if THAT fails, the handle holds
@@ -653,7 +654,8 @@ int set_graph_csr_impl(snn_network_t *net, const uint64_t *row_ptr, const uint32
     // a reward-modulated handle keeps modulating: zeroed traces for the new edges, sized by the committed graph (see above)
     if (net->any_modulation || net->any_conn_kind) TRY(ensure_traces(net));
     if (net->any_conn_kind) TRY(ensure_pending(net));
-    return SNN_OK;
+    // the pairs of an installed edge history are identities, not entries: each finds its entry in the committed arrays, or none
+    return edge_history_resolve(net);
 }
 
 // A CSR built on the device (rows + 1 32-bit offsets, nnz presynaptic indices and weights) becomes the handle's graph: one download,

@@ -25,6 +25,7 @@
 #include "snn_kernels_connect_csr.hpp"
 #include "snn_kernels_csr.hpp"
 #include "snn_kernels_dense_step.hpp"
+#include "snn_kernels_edge_history.hpp"
 #include "snn_kernels_exchange.hpp"
 #include "snn_kernels_graph_merge_csr.hpp"
 #include "snn_kernels_graph_query.hpp"
@@ -471,6 +472,14 @@ struct snn_network {
     hvec<int> want_whist;
     hvec<dev_ptr<float>> whist;
     bool any_whist = false;
+    // edge-weight history (snn_set_edge_history): the pairs of the caller's list in record order on the device -- those of order 1
+    // in slots [0, eh_n1), those of order 2 in [eh_first2, eh_first2 + eh_n2), eh_first2 a multiple of 64; eh_slot[k] is the record
+    // slot of the caller's pair k.  eh_hist: [cap][eh_ld] raw values, NaN for an absent pair
+    hvec<uint32_t> eh_slot;
+    uint32_t eh_n1 = 0, eh_n2 = 0, eh_first2 = 0, eh_ld = 0;
+    dev_ptr<uint32_t> eh_pre, eh_post;                // [eh_ld], record order (the padding slots hold pair (0, 0) and are never recorded)
+    dev_ptr<unsigned long long> eh_offset;            // [eh_ld]: element of W / sell_w, EDGE_HISTORY_ABSENT
+    dev_ptr<float> eh_hist;
     float eeg_ref = 0.007f, eeg_dist = 0.8f, eeg_cond = 251.0f;     // EEGHistory defaults, neuron/mod.rs:246-255
     dev_ptr<float> summ_avg, summ_eeg;                              // [cap][n_lattices]
     uint32_t *spike_counts = nullptr, *lat_first_dev = nullptr, *lat_count_dev = nullptr;
@@ -536,8 +545,11 @@ const StatRow STAT_TABLE[] = {
 
 inline bool recording(const snn_network *net)
 {
-    return net->want_vhist || net->want_raster || net->want_avg || net->want_eeg || net->any_whist;
+    return net->want_vhist || net->want_raster || net->want_avg || net->want_eeg || net->any_whist || net->eh_ld;
 }
+// some record of the weights is on -- a lattice's matrix snapshots or the edge recorder: the step's weight updates happen where
+// step_end's two snapshot points see them (no deferred update, no 24-bit image, no one-launch run, no fast sparse shard step)
+inline bool any_weight_record(const snn_network *net) { return net->any_whist || net->eh_ld != 0; }
 // does the step being computed store its history rows (strided capture: every hist_every-th step)
 inline bool record_now(const snn_network *net)
 {

@@ -85,7 +85,7 @@ inline bool matrix_streamed(const snn_network *net)
 bool stdp_deferral_applies(const snn_network *net)
 {
     if (SNN_HAVE_CUSTOM_MODEL) return false;      // a library carrying generated code keeps the standalone kernels (shorter compile)
-    if (!net->opt.defer_stdp || !net->any_plasticity || net->any_modulation || net->any_whist || !matrix_streamed(net) || net->any_conn_kind ||
+    if (!net->opt.defer_stdp || !net->any_plasticity || net->any_modulation || any_weight_record(net) || !matrix_streamed(net) || net->any_conn_kind ||
         net->lattices.size() > (size_t)STDP_MAX_LATTICES || net->n_loc == 0)
         return false;
     for (size_t l = 0; l < net->lattices.size(); ++l)
@@ -128,7 +128,7 @@ bool dense_close_applies(const snn_network *net);
 bool w24_applies(const snn_network *net)
 {
     return net->w24_enabled && !net->csr && !net->sharded && net->n_loc && net->n_tot && matrix_streamed(net) && net->electrical && !net->chemical &&
-           !net->any_plasticity && !net->any_modulation && !net->any_conn_kind && !net->any_whist && !dense_close_applies(net);
+           !net->any_plasticity && !net->any_modulation && !net->any_conn_kind && !any_weight_record(net) && !dense_close_applies(net);
 }
 
 // the dense input pass in one of its forms: applying the STDP update the previous step deferred, applying its
@@ -503,7 +503,7 @@ int check_reward_cross(snn_network *net)
 int launch_reward_modulation(snn_network *net)
 {
     if (!net->any_modulation || net->nn == 0 || net->n_loc == 0 || !net->trace) return SNN_OK;
-    if (!net->csr && net->opt.defer_rstdp && !net->any_whist && !fused_step_possible(net)) {
+    if (!net->csr && net->opt.defer_rstdp && !any_weight_record(net) && !fused_step_possible(net)) {
         net->rstdp_pending = true;
         net->reward_since_defer = false;
         return SNN_OK;
@@ -823,7 +823,7 @@ bool run_resident_shape(const snn_network *net)
                              !net->cell_list_dev && !SNN_HAVE_CUSTOM_REFRACTORINESS)) &&
            net->n_tot <= RUN_RESIDENT_MAX_NEURONS && (net->electrical || net->chemical) && chem_ok &&
            (!net->any_plasticity || run_resident_stdp_ok(net)) &&
-           !net->any_modulation && !net->any_whist && !net->want_avg && !net->want_eeg && net->hist_every == 1 &&
+           !net->any_modulation && !any_weight_record(net) && !net->want_avg && !net->want_eeg && net->hist_every == 1 &&
            net->model != SNN_MODEL_BCM_IZHIKEVICH && !net->local_inputs_done;
 }
 
@@ -1041,7 +1041,7 @@ bool fused_csr_step_applies(const snn_network *net)
 bool csr_fast_step(const snn_network *net)
 {
     return fused_csr_step_applies(net) && net->sharded && net->x_mode == SNN_EXCHANGE_HALO && !net->any_plasticity &&
-           !net->any_modulation && !net->want_avg && !net->want_eeg && !net->any_whist;
+           !net->any_modulation && !net->want_avg && !net->want_eeg && !any_weight_record(net);
 }
 
 // The spike-train cells advance inside the step's (last) k_step_csr launch: nothing may read a cell's own arrays between the
@@ -1264,7 +1264,18 @@ int step_end(snn_network *net)
     // weight snapshots: order 2 = before the step's weight updates (LatticeNetwork::iterate, neuron/mod.rs:2450-2461),
     // order 1 = after them (a lone Lattice, neuron/mod.rs:904-910)
     auto snapshots = [&](int order) -> int {
-        if (!net->any_whist || !record_now(net)) return SNN_OK;
+        if (!any_weight_record(net) || !record_now(net)) return SNN_OK;
+        // the edge recorder's pairs of this order (k_edge_history): none of them, no launch; a sparse handle without a graph has
+        // no weight array, and every offset is the absent mark
+        const uint32_t eh_first = order == 1 ? 0u : net->eh_first2, eh_count = order == 1 ? net->eh_n1 : net->eh_n2;
+        if (net->eh_ld && eh_count) {
+            const float *weights = net->csr ? net->csr_w.get() : net->W;
+            hipLaunchKernelGGL(k_edge_history, dim3((eh_count + 511u) / 512u), dim3(256), 0, net->stream, weights,
+                               (const unsigned long long *)net->eh_offset.get() + eh_first, eh_count,
+                               net->eh_hist.get() + (size_t)net->cur.hist_steps * net->eh_ld + eh_first);
+            HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+        }
+        if (!net->any_whist) return SNN_OK;
         for (const auto &l : net->lattices) {
             if (net->want_whist[l.slot] != order || l.count == 0) continue;
             float *dst = net->whist[l.slot] + (size_t)net->cur.hist_steps * l.count * l.count;
@@ -1304,7 +1315,7 @@ int grow_history(snn_network *net, uint64_t extra)
     if (!recording(net)) return SNN_OK;
     const uint64_t need = net->cur.hist_steps + (extra + net->hist_every - 1) / net->hist_every + 1;
     if (need <= net->hist_cap && (!net->want_vhist || net->vhist) && (!net->want_raster || net->raster) &&
-        (!net->want_avg || net->summ_avg) && (!net->want_eeg || net->summ_eeg)) {
+        (!net->want_avg || net->summ_avg) && (!net->want_eeg || net->summ_eeg) && (!net->eh_ld || net->eh_hist)) {
         bool ok = true;
         for (const auto &l : net->lattices) ok = ok && (!net->want_whist[l.slot] || net->whist[l.slot] || l.count == 0);
         if (ok) return SNN_OK;
@@ -1328,6 +1339,7 @@ int grow_history(snn_network *net, uint64_t extra)
     TRY(regrow(net->summ_eeg, net->lattices.size() * 4, net->want_eeg));
     for (const auto &l : net->lattices)
         TRY(regrow(net->whist[l.slot], (size_t)l.count * l.count * 4, net->want_whist[l.slot] != 0));
+    TRY(regrow(net->eh_hist, (size_t)net->eh_ld * 4, net->eh_ld != 0));
     net->hist_cap = cap;
     net->stat.history_regrows += 1;
     return SNN_OK;

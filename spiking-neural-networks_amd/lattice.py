@@ -168,6 +168,62 @@ class ConnectingWeights(np.ndarray):
         return super().__getitem__(key)
 
 
+class EdgeHistory:
+    """The weights of a list of edges after (or before) every recorded step: what AdjacencyMatrix::history (graph/mod.rs:278-280)
+    holds for the connecting graph, or for a lattice whose [n, n] snapshots cannot exist -- one column per edge.
+    .edges: the keys, (GraphPosition pre, GraphPosition post) for the connecting graph, (pre index, post index) inside a lattice;
+    .weights float32[steps, n] and .connected bool[steps, n]; len(): the recorded steps; [t]: the dict of step t, absent edges left
+    out; .dense() (a lattice's own history): [steps, size, size], absent edges 0."""
+
+    def __init__(self, edges, weights, connected, pre=None, post=None, size=None):
+        self._edges = edges               # a list, or a callable that builds it when it is first asked for
+        self.weights, self.connected = weights, connected
+        self.pre, self.post, self.size = pre, post, size
+
+    @property
+    def edges(self):
+        if callable(self._edges):
+            self._edges = self._edges()
+        return self._edges
+
+    def __len__(self):
+        return self.weights.shape[0]
+
+    def __getitem__(self, t):
+        edges, w = self.edges, self.weights[t]
+        return {edges[k]: float(w[k]) for k in np.nonzero(self.connected[t])[0]}
+
+    def __iter__(self):
+        return (self[t] for t in range(len(self)))
+
+    def dense(self):
+        if self.size is None:
+            raise TypeError("dense() is for the history of a lattice's own graph")
+        out = np.zeros((len(self), self.size, self.size), np.float32)
+        out[:, self.pre, self.post] = np.where(self.connected, self.weights, np.float32(0))
+        return out
+
+
+def edge_history_plan(segments):
+    """The one list the device's edge recorder takes, from what the façade wants recorded: `segments` is a list of
+    (key, pre, post, when) with global index arrays; returns (pre, post, when, {key: slice}) -- the lists concatenated and, per
+    key, the columns of the recorder's result that are its own."""
+    pre, post, when, columns, at = [], [], [], {}, 0
+    for key, p, q, order in segments:
+        p, q = np.asarray(p, np.int64).reshape(-1), np.asarray(q, np.int64).reshape(-1)
+        if p.size != q.size:
+            raise ValueError("pre and post of a segment must have equal lengths")
+        if order not in (1, 2):
+            raise ValueError("when: 1 after the step's weight updates, 2 before them")
+        pre.append(p)
+        post.append(q)
+        when.append(np.full(p.size, order, np.uint8))
+        columns[key] = slice(at, at + p.size)
+        at += p.size
+    cat = lambda parts, dtype: np.concatenate(parts).astype(dtype) if parts else np.zeros(0, dtype)
+    return cat(pre, np.uint32), cat(post, np.uint32), cat(when, np.uint8), columns
+
+
 class _Neuron(_Record):
     _common = dict(is_spiking=False, last_firing_time=None)
     model = None
@@ -1061,6 +1117,11 @@ class LatticeNetwork:
     def reset_history(self, id):
         self._any(id).reset_history()
 
+    def reset_graph_history(self):                              # neuron/mod.rs:1728-1733: every lattice's graph and the connecting graph
+        for l in self.lattices.values():
+            l.weights_history = np.zeros((0, l.rows * l.cols, l.rows * l.cols), np.float32)
+        self.connecting_graph_history = []
+
     def get_update_grid_history(self, id):
         return self._any(id).update_grid_history
 
@@ -1341,6 +1402,7 @@ class LatticeNetworkGPU:
         self._device = device
         self._dn = None
         self._graph_hist = {}
+        self._edge_hist = None          # what the handle's edge recorder holds: (what was asked for, segments, columns)
         self._plastic = set()           # ids of the lattices that ran with do_plasticity since the upload
         # when a lattice's weight snapshot is taken: 2 = before the step's weight updates (LatticeNetwork::iterate,
         # neuron/mod.rs:2450-2461), 1 = after them (a lone Lattice, neuron/mod.rs:904-910 -- what LatticeGPU passes)
@@ -1406,6 +1468,13 @@ class LatticeNetworkGPU:
         if self._dn is not None:
             self._dn.reset_history()
 
+    def reset_graph_history(self):
+        """every lattice's graph history and the connecting graph's (neuron/mod.rs:1728-1733).  On the device all recorded rows
+        share one step axis, so the record of the whole handle starts afresh, as with reset_history"""
+        self.network.reset_graph_history()
+        if self._dn is not None:
+            self._dn.reset_history()
+
     def set_update_grid_history(self, id, flag):
         self.network.set_update_grid_history(id, flag)
 
@@ -1428,6 +1497,7 @@ class LatticeNetworkGPU:
             self._dn.close()
             self._dn = None
             self._graph_hist = {}
+            self._edge_hist = None
             self._plastic = set()
 
     def _may_differ(self, lattice):
@@ -1612,12 +1682,94 @@ class LatticeNetworkGPU:
         hist = any(l.update_grid_history for l in list(net.lattices.values()) + list(net.spike_train_lattices.values()))
         dn.set_history(voltage=hist, spikes=False)
         for id, l in net.lattices.items():                      # update_graph_history, neuron/mod.rs:572
-            if getattr(l, "update_graph_history", False) != self._graph_hist.get(id, False):
+            # (a dense handle: the [n, n] snapshots; a sparse one: the lattice's stored edges in the edge recorder's list, below)
+            if not self._sparse and getattr(l, "update_graph_history", False) != self._graph_hist.get(id, False):
                 dn.set_graph_history(id, self._graph_hist_order if l.update_graph_history else 0)
                 self._graph_hist[id] = l.update_graph_history
+        self._edge_history_flags()
+
+    def _block_edges(self, key, edges):
+        """(pre, post) global indices of the edges of block (pre_id, post_id) as the handle holds them: a sparse handle filters its
+        stored edges (`edges`: _csr_edges()), a dense one reads the block's rows"""
+        dn = self._dn
+        (first_pre, n_pre), (first_post, n_post) = dn.lattice_range(key[0]), dn.lattice_range(key[1])
+        if self._sparse:
+            pre, post = edges
+            mine = (pre >= first_pre) & (pre < first_pre + n_pre) & (post >= first_post) & (post < first_post + n_post)
+            return pre[mine], post[mine]
+        if n_pre == 0 or n_post == 0:
+            return np.zeros(0, np.int64), np.zeros(0, np.int64)
+        _, c = dn.get_graph_rows(first_pre, n_pre)
+        i, j = np.nonzero(c[:, first_post:first_post + n_post])
+        return i.astype(np.int64) + first_pre, j.astype(np.int64) + first_post
+
+    def _edge_history_flags(self):
+        """One recorder list serves update_connecting_graph_history (order 1: after the step's weight updates, neuron/mod.rs:
+        2463-2465) and, on a sparse handle, update_graph_history of its lattices (order _graph_hist_order): installed when what
+        is asked for changes -- installing restarts the record, as switching a lattice's snapshots on or off does."""
+        dn, net = self._dn, self.network
+        have_graph = bool(dn.n_neurons and dn.n_tot)
+        own = tuple(id for id, l in net.lattices.items()
+                    if self._sparse and getattr(l, "update_graph_history", False) and l.rows * l.cols)
+        asked = (bool(net.update_connecting_graph_history) and have_graph, own)
+        if asked == (self._edge_hist[0] if self._edge_hist else (False, ())):
+            return
+        segments = []
+        edges = self._csr_edges() if self._sparse and (own or (asked[0] and net.connecting_rules)) else None
+        if asked[0]:
+            keys = list(net.connecting)
+            pre = [np.array([self._global(a) for a, _ in keys], np.int64)]
+            post = [np.array([self._global(b) for _, b in keys], np.int64)]
+            for key in net.connecting_rules:                    # record blocks: no dict entry per edge
+                p, q = self._block_edges(key, edges)
+                pre.append(p)
+                post.append(q)
+            segments.append(("connecting", np.concatenate(pre), np.concatenate(post), 1, keys))
+        for id in own:
+            p, q = self._block_edges((id, id), edges)
+            segments.append((id, p, q, self._graph_hist_order, None))
+        pre, post, when, columns = edge_history_plan([s[:4] for s in segments])
+        dn.set_edge_history(pre, post, when)
+        self._edge_hist = (asked, segments, columns) if pre.size else None
+
+    def _position(self, index):
+        """the GraphPosition of global index `index`"""
+        for id, l in list(self.network.lattices.items()) + list(self.network.spike_train_lattices.items()):
+            first, count = self._dn.lattice_range(id)
+            if first <= index < first + count:
+                return GraphPosition(id, divmod(int(index - first), l.cols))
+        raise IndexError(index)
+
+    def _edge_histories(self):
+        """{key: EdgeHistory} of what the edge recorder holds: "connecting", and the id of every lattice of a sparse handle whose
+        own graph is recorded (lattice-local indices)"""
+        if self._edge_hist is None:
+            return {}
+        _, segments, columns = self._edge_hist
+        weights, connected = self._dn.edge_history()
+        out = {}
+        for key, pre, post, _, keys in segments:
+            w, c = weights[:, columns[key]], connected[:, columns[key]]
+            if key == "connecting":
+                def edges(pre=pre, post=post, keys=keys):     # dict entries keep their keys; edges of record blocks get theirs
+                    return keys + [(self._position(p), self._position(q)) for p, q in zip(pre[len(keys):], post[len(keys):])]
+                out[key] = EdgeHistory(edges, w, c)
+            else:
+                first, count = self._dn.lattice_range(key)
+                p, q = pre - first, post - first
+                out[key] = EdgeHistory(lambda p=p, q=q: list(zip(p.tolist(), q.tolist())), w, c, p, q, count)
+        return out
 
     def graph_history(self, id):
-        """[steps][n][n] internal weights of lattice `id` after every step (AdjacencyMatrix::history)."""
+        """The internal weights of lattice `id` at every recorded step (AdjacencyMatrix::history): [steps][n][n] on a dense
+        handle; on a sparse one an EdgeHistory over the lattice's stored edges (lattice-local indices; .dense() builds the
+        [steps][n][n] form of a small lattice)."""
+        if self._sparse:
+            self._ensure()
+            found = self._edge_histories().get(id)
+            if found is None:
+                raise KeyError(f"update_graph_history of lattice {id} was not on in the last run")
+            return found
         return self._ensure().graph_history(id)
 
     def run_lattices(self, iterations):                         # gpu_lattices/mod.rs:3183-3212
@@ -1686,8 +1838,14 @@ class LatticeNetworkGPU:
             if l.update_grid_history and l.rows * l.cols:
                 l.history = dn.voltage_history(id).reshape(-1, l.rows, l.cols)
         for id, l in net.lattices.items():
-            if getattr(l, "update_graph_history", False) and l.rows * l.cols:
+            if not self._sparse and getattr(l, "update_graph_history", False) and l.rows * l.cols:
                 l.weights_history = dn.graph_history(id)
+        for key, h in self._edge_histories().items():
+            if key == "connecting":
+                net.connecting_graph_history = h
+            else:                                               # the [steps, n, n] form only while it is small (256 MiB)
+                small = h.size * h.size * len(h) * 4 <= (256 << 20)
+                net.lattices[key].weights_history = h.dense() if small else h
 
     def history(self, id):
         """[steps][rows][cols] voltages of lattice `id` (GridVoltageHistory, gpu_lattices/mod.rs:189-280)."""

@@ -859,6 +859,33 @@ class DeviceNetwork:
         self._check(self._L.snn_get_graph_history(self._h, id, out.ctypes.data_as(_lib.f32p), out.shape[0]))
         return out
 
+    def set_edge_history(self, pre, post, when=1):
+        """Records the weights of the pairs (pre[k], post[k]) at every recorded step (snn_set_edge_history), dense and sparse
+        handles alike; interleaved global indices, spike-train cells are valid `pre`.  when: 1 after the step's weight updates
+        (the connecting graph, a lone Lattice), 2 before them (a lattice's own graph inside a network); a scalar or one value
+        per pair.  Replaces any earlier list and restarts the record; empty lists switch the recorder off."""
+        p, q = self._pairs(pre, post)
+        given = np.full(p.size, when) if np.ndim(when) == 0 else np.asarray(when).reshape(-1)
+        if given.size != p.size:
+            raise ValueError("when must be a scalar or have one entry per pair")
+        w = np.ascontiguousarray(given, dtype=np.uint8)
+        if np.any(w != given):                   # (what fits a byte goes to the library, which names the offending pair)
+            raise ValueError("when must be 1 or 2")
+        self._check(self._L.snn_set_edge_history(self._h, p.ctypes.data_as(_lib.u32p), q.ctypes.data_as(_lib.u32p),
+                                                w.ctypes.data_as(_lib.u8p), p.size))
+
+    def edge_history_count(self):
+        n = C.c_uint64()
+        self._check(self._L.snn_edge_history_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def edge_history(self):
+        """(weights float32[steps, n], connected bool[steps, n]) of the installed list, in its order; an absent pair reads 0.0 / False"""
+        steps, n = self.history_steps(), self.edge_history_count()
+        w, c = _out((steps, n), np.float32), _out((steps, n), np.uint8)
+        self._check(self._L.snn_get_edge_history(self._h, w.ctypes.data_as(_lib.f32p), c.ctypes.data_as(_lib.u8p), steps))
+        return w, c != 0
+
     def set_history_stride(self, every):
         self._check(self._L.snn_set_history_stride(self._h, int(every)))
 
