@@ -763,7 +763,8 @@ int snn_set_option(snn_network_t *net, const char *name, int value);
  * "image_staged_slices" = slices of the current sparse graph whose window fits, "image_staged_slices_direct" = the same for the image
  * of a shard handle's direct runs, whose halo sources are words of the receive buffer),
  * "steps_sparse_split" (border + interior launches of a shard handle), "steps_dense_close" (k_inputs_dense_close),
- * "steps_two_kernel" (input pass + k_update); and
+ * "steps_two_kernel" (input pass + k_update); "stdp_deferred_steps" (steps whose STDP update was left to the next input
+ * pass, option "defer_stdp" 1 or 3 on a handle where deferral applies); and
  * what happened between run calls: "shadow_refreshes" (the two shadow copies of the exchanged state were rebuilt),
  * "view_refreshes" (the spike-train cells' gap-junction values were recomputed), "history_regrows" (the history buffers
  * were reallocated).  Unknown names fail with SNN_ERR_BAD_ARG. */

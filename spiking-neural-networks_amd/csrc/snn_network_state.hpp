@@ -215,6 +215,7 @@ struct Stats {
     // which form each step took: k_step_resident, k_inputs_dense_close, k_step_csr whole (from the step image), border + interior, input pass + k_update
     uint64_t steps_dense_one_launch = 0, steps_dense_close = 0, steps_sparse_one_launch = 0, steps_sparse_image = 0;
     uint64_t steps_sparse_split = 0, steps_two_kernel = 0;
+    uint64_t stdp_deferred_steps = 0;      // steps whose STDP update was left to the next input pass (or to a flush before it)
     uint64_t shadow_refreshes = 0, view_refreshes = 0, history_regrows = 0;
     uint64_t verify_runs = 0, verify_mismatches = 0, verify_skipped = 0;
 };
@@ -527,6 +528,7 @@ const StatRow STAT_TABLE[] = {
     {"steps_sparse_image", STAT(stat.steps_sparse_image)},
     {"steps_sparse_split", STAT(stat.steps_sparse_split)},
     {"steps_two_kernel", STAT(stat.steps_two_kernel)},
+    {"stdp_deferred_steps", STAT(stat.stdp_deferred_steps)},
     {"shadow_refreshes", STAT(stat.shadow_refreshes)},
     {"view_refreshes", STAT(stat.view_refreshes)},
     {"history_regrows", STAT(stat.history_regrows)},

@@ -362,6 +362,7 @@ int launch_plasticity_kernels(snn_network *net)
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
         net->stdp_pending = true;
         net->stdp_pending_rows_only = true;
+        net->stat.stdp_deferred_steps += 1;
         return SNN_OK;
     }
     if (defer) {
@@ -370,6 +371,7 @@ int launch_plasticity_kernels(snn_network *net)
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
         net->stdp_pending = true;
         if (net->opt.defer_stdp == 2) TRY(flush_stdp(net));      // the prepared deltas applied right away by the scatter passes
+        else net->stat.stdp_deferred_steps += 1;
         return SNN_OK;
     }
     if (net->csr) {
@@ -1320,8 +1322,12 @@ int grow_history(snn_network *net, uint64_t extra)
         for (const auto &l : net->lattices) ok = ok && (!net->want_whist[l.slot] || net->whist[l.slot] || l.count == 0);
         if (ok) return SNN_OK;
     }
-    const uint64_t cap = std::max<uint64_t>(need, net->hist_cap + net->hist_cap / 2);   // geometric: O(T) copies overall
+    // geometric: O(T) copies overall; a capacity that suffices stays (only a buffer is missing: a record was switched on)
+    const uint64_t cap = need <= net->hist_cap ? net->hist_cap : std::max<uint64_t>(need, net->hist_cap + net->hist_cap / 2);
     auto regrow = [&](auto &buf, size_t row_bytes, bool wanted) -> int {
+        // a record that is off gives its buffer up: it holds fewer than `cap` rows, and hist_cap -- the one capacity every buffer
+        // is checked against above -- must not vouch for it when the record is switched on again
+        if (!wanted) buf = nullptr;
         if (!wanted || row_bytes == 0) return SNN_OK;
         std::remove_reference_t<decltype(buf)> nb;
         HIP_TRY(snn_malloc(&nb, std::max<size_t>(256, cap * row_bytes)), SNN_ERR_BUFFER_CREATE);

@@ -169,7 +169,10 @@ def test_mixed_list(snn, csr):
 @pytest.mark.parametrize("form", ["small-dense", "small-sparse", "defer_stdp"])
 def test_every_step_form(snn, form):
     """The list on a 6 x 7 + 5 x 5 electrical network (the one-launch step; the one-launch run while no list is installed) and on
-    a dense handle with defer_stdp on: the oracle's record, and the neuron state the run leaves is the oracle's too."""
+    a dense handle with the option defer_stdp SET: the oracle's record, and the neuron state the run leaves is the oracle's too.
+    At 379 neurons the matrix is not streamed, so stdp_deferral_applies() is false and nothing is deferred with or without a
+    list: the case shows that the option does no harm.  The flush of a pending update by set_edge_history, and deferral standing
+    back while a list is installed, are tested where deferral applies: test_gpu_streamed_walk.py::test_plastic_walk."""
     key, shape = ("main", MAIN) if form == "defer_stdp" else ("small", SMALL)
     pre, post, when, parts, w, c, v, net = reference(key)
     dn = run_device(snn, shape, form == "small-sparse", pre, post, when,
