@@ -684,6 +684,35 @@ int snn_set_edge_history(snn_network_t *net, const uint32_t *pre, const uint32_t
 int snn_get_edge_history(snn_network_t *net, float *weights, uint8_t *connected, size_t steps);
 int snn_edge_history_count(const snn_network_t *net, uint64_t *n);
 
+/* Voltage-peak record: the readout of the reference's GPU experiments (interface_gpu/experiments: find_peaks_above_threshold over
+ * the voltage history of a lattice with update_grid_history, then the peaks at or after a window counted per neuron) kept on the
+ * device as one bit per neuron and recorded step, for neuron lattices of dense AND sparse handles.  The series of a neuron is what
+ * the voltage-history row of every recorded step holds, bit for bit (snn_set_history need not be on); it follows
+ * snn_set_history_stride and restarts with the shared step axis of snn_history_steps (snn_reset_history, a change of stride, any
+ * record switched on or off).  A peak is a local maximum as scipy.signal.find_peaks(x) reports it: x[i-1] < x[i], samples equal
+ * to x[i] up to some r >= i, x[r+1] < x[i]; the index is (i + r) / 2; the first and the last sample are never peaks, a plateau
+ * that reaches the end of the series is none, a NaN sample ends a candidate without a peak; the peak is kept when
+ * x[index] > threshold, compared in binary32.
+ * snn_set_peak_history switches the record of lattice `id` on (enable != 0) or off and sets its threshold; a NaN threshold is
+ * SNN_ERR_BAD_ARG, -inf keeps every peak.  Switching a lattice's record or changing its threshold restarts the step axis, as
+ * snn_set_graph_history does; a call that changes nothing does not.  A handle that is not finalized, or is one of several shards:
+ * SNN_ERR_BAD_STATE (a single-shard handle is covered); a spike-train lattice: SNN_ERR_BAD_ARG.  A call that fails while it
+ * allocates leaves the handle as it was.  While any peak record is on the handle steps as with snn_set_reduced_history's
+ * average on (no one-launch run, no fast sparse shard step) plus one small launch per recorded step (k_peak_detect); with every
+ * record off nothing changes.
+ * A peak is known only once its plateau has ended: peaks whose plateau is still open at the time of a getter call are NOT
+ * reported -- they appear, at their past index, once a later recorded step ends the plateau.
+ * snn_get_peak_raster: [steps][rows*cols] bytes of 0 / 1; steps must equal snn_history_steps (SNN_ERR_DIM_MISMATCH).
+ * snn_get_peak_counts: per neuron the peaks at step indices >= first_step (the experiments' window); count must be rows*cols.
+ * snn_get_peaks: the same peaks as ascending step indices, neuron i's in steps[ptr[i] .. ptr[i+1]); ptr has rows*cols + 1
+ * entries.  *total is always set; ptr and steps are written only when capacity >= *total, otherwise the call returns SNN_OK with
+ * nothing written (the two-call idiom of snn_graph_incoming).  A lattice whose record is off: SNN_ERR_BAD_STATE. */
+int snn_set_peak_history(snn_network_t *net, uint32_t id, int enable, float threshold);
+int snn_get_peak_raster(snn_network_t *net, uint32_t id, uint8_t *dst, size_t steps);
+int snn_get_peak_counts(snn_network_t *net, uint32_t id, uint64_t first_step, uint32_t *dst, size_t count);
+int snn_get_peaks(snn_network_t *net, uint32_t id, uint64_t first_step, uint64_t *ptr, uint32_t *steps, uint64_t capacity,
+                  uint64_t *total);
+
 /* Strided capture: store the history rows (voltage, raster, reduced rows) of every `every`-th step only -- steps
  * 0, every, 2*every, ... counted from the last (re)start of the record; 1 = every step (the reference's
  * behaviour).  Changing the stride restarts the record.  Spike totals (below) always count every step. */

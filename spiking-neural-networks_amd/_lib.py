@@ -288,6 +288,10 @@ SIGNATURES = {
     "snn_set_edge_history": (C.c_int, [H, u32p, u32p, u8p, C.c_size_t]),
     "snn_get_edge_history": (C.c_int, [H, f32p, u8p, C.c_size_t]),
     "snn_edge_history_count": (C.c_int, [H, u64p]),
+    "snn_set_peak_history": (C.c_int, [H, C.c_uint32, C.c_int, C.c_float]),
+    "snn_get_peak_raster": (C.c_int, [H, C.c_uint32, u8p, C.c_size_t]),
+    "snn_get_peak_counts": (C.c_int, [H, C.c_uint32, C.c_uint64, u32p, C.c_size_t]),
+    "snn_get_peaks": (C.c_int, [H, C.c_uint32, C.c_uint64, u64p, u32p, C.c_uint64, u64p]),
     "snn_set_history_stride": (C.c_int, [H, C.c_uint32]),
     "snn_set_reduced_history": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]),
     "snn_get_average_voltage_history": (C.c_int, [H, C.c_uint32, f32p, C.c_size_t]),

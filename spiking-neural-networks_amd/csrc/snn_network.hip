@@ -11,6 +11,7 @@
 #include "snn_network_verify.hpp"
 #include "snn_network_graph.hpp"
 #include "snn_network_edge_history.hpp"
+#include "snn_network_peaks.hpp"
 
 // ================================================================================================
 // C ABI
@@ -940,6 +941,20 @@ int snn_edge_history_count(const snn_network_t *net, uint64_t *n) ABI_TRY
 }
 ABI_CATCH
 
+int snn_set_peak_history(snn_network_t *net, uint32_t id, int enable, float threshold) ABI_TRY
+{ return set_peak_history(net, id, enable, threshold); }
+ABI_CATCH
+int snn_get_peak_raster(snn_network_t *net, uint32_t id, uint8_t *dst, size_t steps) ABI_TRY
+{ return get_peak_raster(net, id, dst, steps); }
+ABI_CATCH
+int snn_get_peak_counts(snn_network_t *net, uint32_t id, uint64_t first_step, uint32_t *dst, size_t count) ABI_TRY
+{ return get_peak_counts(net, id, first_step, dst, count); }
+ABI_CATCH
+int snn_get_peaks(snn_network_t *net, uint32_t id, uint64_t first_step, uint64_t *ptr, uint32_t *steps, uint64_t capacity,
+                  uint64_t *total) ABI_TRY
+{ return get_peaks(net, id, first_step, ptr, steps, capacity, total); }
+ABI_CATCH
+
 int snn_set_history_stride(snn_network_t *net, uint32_t every) ABI_TRY
 {
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
@@ -1119,7 +1134,14 @@ int snn_debug_checkpoint(snn_network_t *net, int restore) ABI_TRY
     size_t total = 0;
     for (const auto &a : arrays) total += a.second;
     if (total > ((size_t)256 << 20)) return fail(SNN_ERR_BAD_STATE, "checkpoints are for small handles (256 MiB of device state at most)");
+    // the peak raster is a history a later step writes BACKWARDS into (a plateau's peak lands in a past row): its rows so far belong
+    // to the checkpoint, wherever the raster has been regrown to by the time of the restore
+    const size_t peak_words = (net->want_peaks && net->pk_raster) ? (size_t)net->cur.hist_steps * (net->n_pad / 64) : 0;
     if (!restore) {
+        hvec<unsigned long long> peak_rows(peak_words);
+        if (peak_words) HIP_TRY(copy_sync(net, peak_rows.data(), net->pk_raster, peak_words * 8, hipMemcpyDeviceToHost), SNN_ERR_BUFFER_READ);
+        cp.peak_rows.swap(peak_rows);
+        cp.peak_epoch = net->pk_epoch;
         cp.arrays.clear();
         for (const auto &a : arrays) {
             cp.arrays.emplace_back(a.first, hvec<uint8_t>(a.second));
@@ -1131,6 +1153,7 @@ int snn_debug_checkpoint(snn_network_t *net, int restore) ABI_TRY
         return SNN_OK;
     }
     if (!cp.valid) return fail(SNN_ERR_BAD_STATE, "no checkpoint was taken");
+    if (cp.peak_epoch != net->pk_epoch) return fail(SNN_ERR_BAD_STATE, "the handle's structure changed since the checkpoint (peak records switched)");
     // every array of the checkpoint must still be the handle's (arrays allocated since -- shadows, views, granules -- are caches
     // whose validity flags are put back below)
     std::map<void *, size_t> current(arrays.begin(), arrays.end());
@@ -1142,6 +1165,8 @@ int snn_debug_checkpoint(snn_network_t *net, int restore) ABI_TRY
     for (const auto &a : cp.arrays)
         HIP_TRY(hipMemcpyAsync(a.first, a.second.data(), a.second.size(), hipMemcpyHostToDevice, net->stream), SNN_ERR_BUFFER_WRITE);
     HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
+    if (!cp.peak_rows.empty())
+        HIP_TRY(copy_sync(net, net->pk_raster, cp.peak_rows.data(), cp.peak_rows.size() * 8, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
     net->st_clock = cp.st_clock; net->cur = cp.cur; net->cache = cp.cache; net->opt.persistent_run = cp.persistent_run;
     net->stdp_pending = false; net->stdp_pending_rows_only = false; net->rstdp_pending = false; net->reward_since_defer = false;
     net->cells_stepped = false; net->local_inputs_done = false; net->run_tag = 1;

@@ -32,6 +32,7 @@
 #include "snn_kernels_graph_query_csr.hpp"
 #include "snn_kernels_inputs.hpp"
 #include "snn_kernels_misc.hpp"
+#include "snn_kernels_peaks.hpp"
 #include "snn_kernels_resident.hpp"
 #include "snn_kernels_update.hpp"
 #include "snn_layout.hpp"
@@ -444,6 +445,8 @@ struct snn_network {
         Cursors cur;
         CacheState cache;
         uint32_t persistent_run = 1;
+        hvec<unsigned long long> peak_rows;       // the peak raster's rows so far: later steps set bits in PAST rows
+        uint64_t peak_epoch = 0;
     } checkpoint;
     unsigned long long *run_timing = nullptr;   // SNN_AMD_RUN_TIMING=1 or option "run_timing": phase clocks of k_run_resident
     unsigned long long run_timing_last[4] = {0, 0, 0, 0};   // workgroup 0, last launch: poll, barrier, turns, update + publish
@@ -481,6 +484,16 @@ struct snn_network {
     dev_ptr<uint32_t> eh_pre, eh_post;                // [eh_ld], record order (the padding slots hold pair (0, 0) and are never recorded)
     dev_ptr<unsigned long long> eh_offset;            // [eh_ld]: element of W / sell_w, EDGE_HISTORY_ABSENT
     dev_ptr<float> eh_hist;
+    // voltage-peak record (snn_set_peak_history, snn_kernels_peaks.hpp): per neuron lattice slot {record on, threshold bits} on the host
+    // and on the device, the streaming state per neuron -- registered arrays (dev_alloc): snapshots and checkpoints carry them --
+    // and the raster [cap][n_pad / 64], grown with the other records.  pk_epoch counts the calls that changed the settings
+    hvec<uint2> pk_cfg_host;
+    dev_ptr<uint2> pk_cfg;
+    bool want_peaks = false;
+    float *pk_prev = nullptr;
+    uint32_t *pk_left = nullptr;
+    dev_ptr<unsigned long long> pk_raster;
+    uint64_t pk_epoch = 0;
     float eeg_ref = 0.007f, eeg_dist = 0.8f, eeg_cond = 251.0f;     // EEGHistory defaults, neuron/mod.rs:246-255
     dev_ptr<float> summ_avg, summ_eeg;                              // [cap][n_lattices]
     uint32_t *spike_counts = nullptr, *lat_first_dev = nullptr, *lat_count_dev = nullptr;
@@ -547,7 +560,7 @@ const StatRow STAT_TABLE[] = {
 
 inline bool recording(const snn_network *net)
 {
-    return net->want_vhist || net->want_raster || net->want_avg || net->want_eeg || net->any_whist || net->eh_ld;
+    return net->want_vhist || net->want_raster || net->want_avg || net->want_eeg || net->want_peaks || net->any_whist || net->eh_ld;
 }
 // some record of the weights is on -- a lattice's matrix snapshots or the edge recorder: the step's weight updates happen where
 // step_end's two snapshot points see them (no deferred update, no 24-bit image, no one-launch run, no fast sparse shard step)

@@ -825,7 +825,7 @@ bool run_resident_shape(const snn_network *net)
                              !net->cell_list_dev && !SNN_HAVE_CUSTOM_REFRACTORINESS)) &&
            net->n_tot <= RUN_RESIDENT_MAX_NEURONS && (net->electrical || net->chemical) && chem_ok &&
            (!net->any_plasticity || run_resident_stdp_ok(net)) &&
-           !net->any_modulation && !any_weight_record(net) && !net->want_avg && !net->want_eeg && net->hist_every == 1 &&
+           !net->any_modulation && !any_weight_record(net) && !net->want_avg && !net->want_peaks && !net->want_eeg && net->hist_every == 1 &&
            net->model != SNN_MODEL_BCM_IZHIKEVICH && !net->local_inputs_done;
 }
 
@@ -1043,7 +1043,7 @@ bool fused_csr_step_applies(const snn_network *net)
 bool csr_fast_step(const snn_network *net)
 {
     return fused_csr_step_applies(net) && net->sharded && net->x_mode == SNN_EXCHANGE_HALO && !net->any_plasticity &&
-           !net->any_modulation && !net->want_avg && !net->want_eeg && !any_weight_record(net);
+           !net->any_modulation && !net->want_avg && !net->want_peaks && !net->want_eeg && !any_weight_record(net);
 }
 
 // The spike-train cells advance inside the step's (last) k_step_csr launch: nothing may read a cell's own arrays between the
@@ -1303,6 +1303,15 @@ int step_end(snn_network *net)
         hipLaunchKernelGGL(k_lattice_summary, dim3((unsigned)nl), dim3(256), 0, net->stream, sa);
         HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
     }
+    if (net->want_peaks && record_now(net)) {
+        // the voltage plane the history row of this step was written from; peaks found now set bits in earlier rows (k_peak_detect)
+        PeakArgs pa{};
+        pa.xbuf = net->xbuf; pa.xl = net->xl; pa.lattice_slot = net->lattice_slot; pa.cfg = net->pk_cfg;
+        pa.prev = net->pk_prev; pa.left = net->pk_left; pa.raster = net->pk_raster;
+        pa.n_neurons = net->nn; pa.n_pad = net->n_pad; pa.words = net->n_pad / 64; pa.t = (uint32_t)net->cur.hist_steps;
+        hipLaunchKernelGGL(k_peak_detect, dim3(net->n_pad / 256), dim3(256), 0, net->stream, pa);
+        HIP_TRY(hipGetLastError(), SNN_ERR_QUEUE);
+    }
     net->cur.clock += 1;
     if (!net->cells_stepped) TRY(launch_spike_trains(net, 1, net->cur.run_step_offset, net->cur.clock));
     net->cells_stepped = false;
@@ -1316,8 +1325,11 @@ int grow_history(snn_network *net, uint64_t extra)
 {
     if (!recording(net)) return SNN_OK;
     const uint64_t need = net->cur.hist_steps + (extra + net->hist_every - 1) / net->hist_every + 1;
+    if (net->want_peaks && need >= 0xFFFFFFFFull)
+        return fail(SNN_ERR_BAD_STATE, "a peak record holds fewer than 2^32-1 rows: reset the history or record with a stride");
     if (need <= net->hist_cap && (!net->want_vhist || net->vhist) && (!net->want_raster || net->raster) &&
-        (!net->want_avg || net->summ_avg) && (!net->want_eeg || net->summ_eeg) && (!net->eh_ld || net->eh_hist)) {
+        (!net->want_avg || net->summ_avg) && (!net->want_eeg || net->summ_eeg) && (!net->eh_ld || net->eh_hist) &&
+        (!net->want_peaks || net->pk_raster)) {
         bool ok = true;
         for (const auto &l : net->lattices) ok = ok && (!net->want_whist[l.slot] || net->whist[l.slot] || l.count == 0);
         if (ok) return SNN_OK;
@@ -1346,6 +1358,20 @@ int grow_history(snn_network *net, uint64_t extra)
     for (const auto &l : net->lattices)
         TRY(regrow(net->whist[l.slot], (size_t)l.count * l.count * 4, net->want_whist[l.slot] != 0));
     TRY(regrow(net->eh_hist, (size_t)net->eh_ld * 4, net->eh_ld != 0));
+    if (net->want_peaks) {
+        // the peak raster: rows of the record so far kept, every other row zeroed (k_peak_detect clears a row again when it is recorded)
+        const size_t row_bytes = (size_t)(net->n_pad / 64) * 8;
+        dev_ptr<unsigned long long> nb;
+        HIP_TRY(snn_malloc(&nb, cap * row_bytes), SNN_ERR_BUFFER_CREATE);
+        HIP_TRY(hipMemsetAsync(nb, 0, cap * row_bytes, net->stream), SNN_ERR_BUFFER_WRITE);
+        if (net->pk_raster && net->cur.hist_steps)
+            HIP_TRY(hipMemcpyAsync(nb, net->pk_raster, net->cur.hist_steps * row_bytes, hipMemcpyDeviceToDevice, net->stream),
+                    SNN_ERR_BUFFER_WRITE);
+        HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
+        net->pk_raster = std::move(nb);
+    } else {
+        net->pk_raster = nullptr;
+    }
     net->hist_cap = cap;
     net->stat.history_regrows += 1;
     return SNN_OK;

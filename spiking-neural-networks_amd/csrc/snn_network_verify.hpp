@@ -52,7 +52,8 @@ std::string describe_array(const snn_network *net, const void *ptr, uint32_t wor
         {net->uni_neuron, "uniform table (neurons)"}, {net->uni_cell, "uniform table (cells)"}, {net->ca.presyn_value, "cells: presyn_value"},
         {net->ca.seed, "cells: seed"}, {net->ca.step, "cells: step"}, {net->ca.counter, "cells: counter"}, {net->lattice_slot, "lattice_slot"},
         {net->csr_w, "sparse weights"}, {net->trace, "traces"}, {net->pending, "dw of reward-modulated connections"},
-        {net->edge_counter, "counters of reward-modulated connections"}};
+        {net->edge_counter, "counters of reward-modulated connections"},
+        {net->pk_prev, "peak record: previous sample"}, {net->pk_left, "peak record: left edge"}};
     for (const auto &k : known)
         if (k.base == ptr) return std::string(k.name) + ", word " + std::to_string(word);
     for (const auto *table : {&net->neuron_attrs, &net->cell_attrs})

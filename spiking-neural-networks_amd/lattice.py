@@ -1404,6 +1404,8 @@ class LatticeNetworkGPU:
         self._graph_hist = {}
         self._edge_hist = None          # what the handle's edge recorder holds: (what was asked for, segments, columns)
         self._plastic = set()           # ids of the lattices that ran with do_plasticity since the upload
+        self._peak_settings = {}        # set_peak_history: lattice id -> threshold; kept across uploads of a fresh handle
+        self._peak_applied = {}         # ... and what the current handle has been told
         # when a lattice's weight snapshot is taken: 2 = before the step's weight updates (LatticeNetwork::iterate,
         # neuron/mod.rs:2450-2461), 1 = after them (a lone Lattice, neuron/mod.rs:904-910 -- what LatticeGPU passes)
         self._graph_hist_order = graph_history_order
@@ -1499,6 +1501,7 @@ class LatticeNetworkGPU:
             self._graph_hist = {}
             self._edge_hist = None
             self._plastic = set()
+            self._peak_applied = {}
 
     def _may_differ(self, lattice):
         """whether the handle's weights of a rule-held lattice may differ from what its rule gives: plasticity (STDP, BCM) was on
@@ -1687,6 +1690,7 @@ class LatticeNetworkGPU:
                 dn.set_graph_history(id, self._graph_hist_order if l.update_graph_history else 0)
                 self._graph_hist[id] = l.update_graph_history
         self._edge_history_flags()
+        self._peak_flags()
 
     def _block_edges(self, key, edges):
         """(pre, post) global indices of the edges of block (pre_id, post_id) as the handle holds them: a sparse handle filters its
@@ -1873,6 +1877,49 @@ class LatticeNetworkGPU:
         l = self.network.lattices[id]
         return self._dn.spike_counts(id).reshape(l.rows, l.cols)
 
+    # The experiments' readout kept on the device (interface_gpu/experiments: find_peaks_above_threshold over a lattice's voltage
+    # history, then the peaks at or after a window counted per neuron) -- one bit per neuron and step instead of the history.
+    def set_peak_history(self, id, threshold=20.0, enable=True):
+        """Voltage-peak record of lattice `id`; the setting outlives the device copy (a builder call uploads a fresh handle and
+        the record is switched on again there).  Switching it, or a new threshold, restarts the records of the handle."""
+        if id not in self.network.lattices:
+            raise KeyError(f"no neuron lattice {id}")
+        threshold = float(np.float32(threshold))
+        if threshold != threshold:
+            raise ValueError("the threshold is NaN")
+        if enable:
+            self._peak_settings[id] = threshold
+        else:
+            self._peak_settings.pop(id, None)
+        if self._dn is not None:
+            self._peak_flags()
+
+    def _peak_flags(self):
+        dn = self._dn
+        for id in sorted(set(self._peak_settings) | set(self._peak_applied)):
+            want = self._peak_settings.get(id) if id in self.network.lattices else None
+            if want != self._peak_applied.get(id):
+                dn.set_peak_history(id, 0.0 if want is None else want, want is not None)
+                if want is None:
+                    self._peak_applied.pop(id, None)
+                else:
+                    self._peak_applied[id] = want
+
+    def peaks(self, id):
+        """per neuron (row-major) the list of step indices of its voltage peaks above the threshold: element for element the
+        experiments' [find_peaks_above_threshold([j[i] for j in data], threshold) for i in range(n)] over history(id)"""
+        l = self.network.lattices[id]
+        if self._dn is None:
+            return [[] for _ in range(l.rows * l.cols)]
+        return [p.tolist() for p in self._dn.peaks(id)]
+
+    def peak_counts(self, id, window=0):
+        """[rows][cols]: per neuron len([j for j in peaks if j >= window])"""
+        l = self.network.lattices[id]
+        if self._dn is None:
+            return np.zeros((l.rows, l.cols), np.uint32)
+        return self._dn.peak_counts(id, window).reshape(l.rows, l.cols)
+
     def close(self):
         self._dirty()
 
@@ -1886,6 +1933,7 @@ class LatticeGPU:
         self._device = device
         self._sparse = bool(sparse)                                 # the handle holds a sparse (CSR) graph
         self._net = None
+        self._peak_setting = None                                   # set_peak_history: the threshold, None while off
 
     @classmethod
     def from_lattice(cls, lattice, device=0, sparse=False):     # gpu_lattices/mod.rs:496-511
@@ -1897,6 +1945,8 @@ class LatticeGPU:
         if self._net is None:
             host = LatticeNetwork.generate_network([self._lattice])
             self._net = LatticeNetworkGPU(host, device=self._device, graph_history_order=1, sparse=self._sparse)
+            if self._peak_setting is not None:
+                self._net.set_peak_history(self._lattice.id, self._peak_setting)
         return self._net
 
     def _dirty(self):
@@ -1970,6 +2020,25 @@ class LatticeGPU:
     def reset_history(self):
         if self._net is not None:
             self._net.reset_history()
+
+    def set_peak_history(self, threshold=20.0, enable=True):
+        """the voltage-peak record of the lattice (LatticeNetworkGPU.set_peak_history); kept across rebuilds of the device copy"""
+        threshold = float(np.float32(threshold))
+        if threshold != threshold:
+            raise ValueError("the threshold is NaN")
+        self._peak_setting = threshold if enable else None
+        if self._net is not None:
+            self._net.set_peak_history(self._lattice.id, threshold, enable)
+
+    def peaks(self):
+        if self._net is None:
+            return [[] for _ in range(self._lattice.rows * self._lattice.cols)]
+        return self._net.peaks(self._lattice.id)
+
+    def peak_counts(self, window=0):
+        if self._net is None:
+            return np.zeros((self._lattice.rows, self._lattice.cols), np.uint32)
+        return self._net.peak_counts(self._lattice.id, window)
 
     def reset_timing(self):
         if self._net is not None:

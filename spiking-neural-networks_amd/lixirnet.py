@@ -14,6 +14,9 @@ so that the procedure of the reference's own Python tests (interface_gpu/lixirne
 against it unchanged apart from the import (`from snn_amd import lixirnet as ln`).  The `*Lattice` / `*Network`
 classes only build; stepping lives on the `*GPU` classes (there is no CPU stepper in this package).
 
+Beyond the reference's methods the two `*GPU` classes carry the device-side readout of its experiments
+(`set_peak_history`, `peaks`, `peak_counts`: find_peaks_above_threshold without the voltage history).
+
 The library is compiled the first time one of the names is touched (hipcc, about a minute, once per checkout).
 """
 import ctypes as _C

@@ -886,6 +886,40 @@ class DeviceNetwork:
         self._check(self._L.snn_get_edge_history(self._h, w.ctypes.data_as(_lib.f32p), c.ctypes.data_as(_lib.u8p), steps))
         return w, c != 0
 
+    def set_peak_history(self, id, threshold, enable=True):
+        """Voltage-peak record of neuron lattice `id` (snn_set_peak_history): one bit per neuron and recorded step where
+        scipy.signal.find_peaks of the recorded voltage series has a peak above `threshold` -- the experiments'
+        find_peaks_above_threshold, kept on the device.  Switching it or changing the threshold restarts the record."""
+        self._check(self._L.snn_set_peak_history(self._h, id, int(bool(enable)), float(threshold)))
+
+    def peak_raster(self, id):
+        """bool[steps, rows*cols]; peaks whose plateau is still open are not in it yet"""
+        rows, cols, _ = self.lattices[id]
+        out = _out((self.history_steps(), rows * cols), np.uint8)
+        self._check(self._L.snn_get_peak_raster(self._h, id, out.ctypes.data_as(_lib.u8p), out.shape[0]))
+        return out != 0
+
+    def peak_counts(self, id, first_step=0):
+        """uint32[rows*cols]: per neuron the peaks at step indices >= first_step"""
+        rows, cols, _ = self.lattices[id]
+        out = _out(rows * cols, np.uint32)
+        self._check(self._L.snn_get_peak_counts(self._h, id, int(first_step), out.ctypes.data_as(_lib.u32p), out.size))
+        return out
+
+    def peaks(self, id, first_step=0):
+        """per neuron (row-major) the ascending step indices >= first_step of its peaks, a list of int arrays"""
+        rows, cols, _ = self.lattices[id]
+        total = C.c_uint64()
+        ptr, steps = np.zeros(rows * cols + 1, np.uint64), np.zeros(0, np.uint32)
+        for _ in range(2):                       # the two-call idiom: the total first, then the lists
+            self._check(self._L.snn_get_peaks(self._h, id, int(first_step), ptr.ctypes.data_as(_lib.u64p),
+                                              steps.ctypes.data_as(_lib.u32p), steps.size, C.byref(total)))
+            if total.value <= steps.size:
+                break
+            steps = np.zeros(int(total.value), np.uint32)
+        flat = steps.astype(np.int64)
+        return [flat[int(ptr[i]):int(ptr[i + 1])] for i in range(rows * cols)]
+
     def set_history_stride(self, every):
         self._check(self._L.snn_set_history_stride(self._h, int(every)))
 
