@@ -20,6 +20,7 @@
 #include "snn_kernels_misc.hpp"
 #include "snn_kernels_reward.hpp"
 #include "snn_kernels_update.hpp"
+#include "snn_step_image_plan.hpp"     // SELL_PAD, PLAN_CODE, the IMG_ constants and the host-built half of the step image
 
 namespace snn {
 
@@ -27,8 +28,7 @@ namespace snn {
 #define SNN_CSR_PREFETCH 0
 #endif
 constexpr bool CSR_PREFETCH = SNN_CSR_PREFETCH != 0;     // (A/B switch of the build: profiles/r05/README.md)
-constexpr uint32_t SELL_PAD = 0xFFFFFFFFu;     // presynaptic index of a padding entry
-constexpr uint32_t PLAN_CODE = 0x7FFFFFFFu;    // gather-plan word: the source code (all ones = padding), bit 31 = new chunk
+static_assert(PLAN_CHUNK == (uint32_t)CHUNK, "the plan's chunk bits follow the canonical reduction chunk");
 
 // peer form: where a poll that gives up says so (see peer_give_up)
 struct PeerFailure { uint32_t *word[2]; };
@@ -284,12 +284,11 @@ __device__ __forceinline__ void csr_row_sums(const CsrInputsArgs &a, uint32_t q,
 //     than IMG_MAX_PIECES pieces (an unstructured graph) has no pieces: its plan words are the plain codes and the rows gather
 //     from global memory as before -- still through 16-byte records.
 // The sums are the canonical ones (ascending, chunk flush): bit-identical to csr_row_sums and to the dense kernel.
-constexpr uint32_t IMG_HDR_WORDS = 40, IMG_MAX_PIECES = 16, IMG_PIECE_WORDS = 64, IMG_CELL_BIT = 0x40000000u;
+// (IMG_HDR_WORDS, IMG_MAX_PIECES, IMG_PIECE_WORDS, IMG_CELL_BIT, IMG_WIN_WORDS = LDS words per wavefront: snn_step_image_plan.hpp)
 #ifndef SNN_IMG_RING
 #define SNN_IMG_RING 4
 #endif
 constexpr uint32_t IMG_RING = SNN_IMG_RING;               // records (16 B each) a lane keeps in flight; even
-constexpr uint32_t IMG_WIN_WORDS = IMG_MAX_PIECES * IMG_PIECE_WORDS;           // LDS words per wavefront
 struct CsrImage {
     const uint32_t *hdr;         // [n_slices][IMG_HDR_WORDS]; null: the launch takes the plain form
     const uint4 *rec;
@@ -321,8 +320,14 @@ __device__ __forceinline__ void csr_img_sums(const InputsArgs &in, const uint4 *
                 const bool is_pad = (word[e] & PLAN_CODE) == PLAN_CODE;
                 if (STAGED) {
                     const uint32_t off = is_pad ? 0u : (word[e] & 0xFFFFu);
-                    v[e] = __uint_as_float(win[off]);
-                    silent[e] = win[off + 1u];                               // (read for every entry: branch-free; used for cells)
+                    // two neighbouring words for every entry, branch-free, as ONE ds_read2_b32 (the second is used for cells).  The
+                    // pair never leaves the window: a neuron in the window's last word reads the pair in front of it and takes
+                    // its second word (a cell's two words end at IMG_WIN_WORDS - 1 at the latest).  Clamping the second index
+                    // alone splits the pair into two LDS reads: 0.5 % of the step at BASELINE configs[4]
+                    const uint32_t at = min(off, IMG_WIN_WORDS - 2u);
+                    const uint32_t w0 = win[at], w1 = win[at + 1u];
+                    v[e] = __uint_as_float(off > at ? w1 : w0);
+                    silent[e] = w1;
                 } else {
                     // an unstaged slice: the plain codes, gathered from the exchanged state / the cells' view
                     const uint32_t code = word[e] & PLAN_CODE;
@@ -398,7 +403,9 @@ __device__ __forceinline__ void csr_row_sums_img(const CsrInputsArgs &a, const C
         if (lane < words)
             __builtin_amdgcn_global_load_lds(src + lane, (__attribute__((address_space(3))) uint32_t *)(win + u * IMG_PIECE_WORDS), 4, 0, 0);
     }
-    __builtin_amdgcn_s_waitcnt(0x0070 | 0x0F00 | 0xC000);         // vmcnt(0): records and window have landed (expcnt / lgkmcnt left alone)
+    // vmcnt(0): records and window have landed; expcnt / lgkmcnt left alone.  The immediate on gfx9: vmcnt is bits 3:0 AND 15:14
+    // (all zero here), expcnt bits 6:4 (7 = no wait), lgkmcnt bits 11:8 (15 = no wait)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
     __builtin_amdgcn_wave_barrier();                              // (one wavefront fills and reads its own window: no workgroup barrier)
     if (n_pieces) csr_img_sums<true>(in, rec, pairs, win, xv, cv, a.g.halo, a.g.halo_base, vq, gq, r, sum);
     else csr_img_sums<false>(in, rec, pairs, win, xv, cv, a.g.halo, a.g.halo_base, vq, gq, r, sum);

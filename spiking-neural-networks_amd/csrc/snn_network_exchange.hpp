@@ -230,7 +230,7 @@ int ensure_exchange_plan(snn_network *net)
             if (net->direct_capable && P == 1 && !net->sell_pre_host.empty()) {
                 hvec<uint32_t> img_hdr, plan_win;
                 uint64_t records = 0;
-                build_step_image_plan(net, net->slice_ptr_host, net->sell_pre_host, n_slices, img_hdr, plan_win, records, net->img_staged_slices_direct,
+                build_step_image_plan(net->nn, net->nc, net->slice_ptr_host, net->sell_pre_host, n_slices, img_hdr, plan_win, records, net->img_staged_slices_direct,
                                       halo_word.data());
                 TRY(upload_table(net, &net->csr_img_hdr_direct, img_hdr));
                 TRY(upload_table(net, &net->csr_plan_win_direct, plan_win));

@@ -599,7 +599,7 @@ int set_graph_csr_impl(snn_network_t *net, const uint64_t *row_ptr, const uint32
     {
         // the step image's host-built half: slice headers with the window pieces, and the plan words that go with them
         hvec<uint32_t> img_hdr, plan_win;
-        build_step_image_plan(net, slice_ptr, sell_pre, n_slices, img_hdr, plan_win, img_records, img_staged_slices);
+        build_step_image_plan(net->nn, net->nc, slice_ptr, sell_pre, n_slices, img_hdr, plan_win, img_records, img_staged_slices);
         TRY(up(&img_hdr_d, img_hdr.data(), img_hdr.size() * 4));
         TRY(up(&plan_win_d, plan_win.data(), plan_win.size() * 4));
         HIP_TRY(snn_malloc(&img_rec_d, (size_t)img_records * 16 + 4096), SNN_ERR_BUFFER_CREATE);    // (+ a wavefront's load of slack)
