@@ -854,7 +854,10 @@ int snn_set_synthetic_drive(snn_network_t *net, uint64_t seed, float fraction, f
 /* ALGORITHMIC bytes ONE launch of the synaptic-input kernel moves (DESIGN.md "Roofline"; what the step has to move, not
  * what the counters saw): 4 B per synapse of the shard (dense) -- 3 B while the next plain step reads the 24-bit image of a
  * static matrix instead of W (built by the first run after the graph was set, so the figure of a handle
- * that has not run yet is the 4 B one; SNN_AMD_W24=0 keeps W); 8 B per stored synapse (sparse) + S bytes of state per OWNED
+ * that has not run yet is the 4 B one; SNN_AMD_W24=0 keeps W.  An image of 1 GiB and more is stored in the allocation W's
+ * placement search chose -- W moves to a fresh allocation of its size while the weights stay static and back into its own when
+ * they stop being so, so a handle holds two W-sized allocations meanwhile; SNN_AMD_W24_REGION=0 keeps the image in a fresh
+ * allocation of its own size); 8 B per stored synapse (sparse) + S bytes of state per OWNED
  * row when the launch is the one-launch step k_step_csr, which also is the neuron update (S by model: Izhikevich 60, leaky
  * 68, Hodgkin-Huxley 140, ...; + 44 B per live transmitter type with chemical synapses) + 28 B per spike-train cell when
  * the cells advance in that launch too; 16 B per internal synapse of a reward-modulated lattice whose weight update rides

@@ -52,6 +52,8 @@ int snn_network_create(int device, int neuron_model, int nt_kinetics, int recept
     net->model = neuron_model; net->nt_kind = nt_kinetics; net->rc_kind = receptor_kinetics;
     net->st_kind = spike_train_model;
     if (const char *e = getenv("SNN_AMD_W24")) net->w24_enabled = !(e[0] == '0' && e[1] == '\0');      // (outside the option table, like SNN_AMD_CONTIGUOUS)
+    if (const char *e = getenv("SNN_AMD_W24_REGION")) net->w24_region_enabled = !(e[0] == '0' && e[1] == '\0');
+    if (const char *e = getenv("SNN_AMD_W24_REGION_MIN")) net->w24_region_min = std::min<size_t>(net->w24_region_min, strtoull(e, nullptr, 0));
     if (hipStreamCreateWithFlags(&net->own_stream, hipStreamNonBlocking) != hipSuccess) {
         delete net;
         return fail(SNN_ERR_QUEUE, "hipStreamCreate failed");
@@ -1149,6 +1151,7 @@ int snn_debug_checkpoint(snn_network_t *net, int restore) ABI_TRY
         }
         HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
         cp.st_clock = net->st_clock; cp.cur = net->cur; cp.cache = net->cache; cp.persistent_run = net->opt.persistent_run;
+        cp.matrix = net->W;
         cp.valid = true;
         return SNN_OK;
     }
@@ -1156,14 +1159,16 @@ int snn_debug_checkpoint(snn_network_t *net, int restore) ABI_TRY
     if (cp.peak_epoch != net->pk_epoch) return fail(SNN_ERR_BAD_STATE, "the handle's structure changed since the checkpoint (peak records switched)");
     // every array of the checkpoint must still be the handle's (arrays allocated since -- shadows, views, granules -- are caches
     // whose validity flags are put back below)
+    // (W is the one array that moves without a structural call: out of and back into its first region, ensure_w24)
+    auto now_at = [&](void *then) { return (then && then == cp.matrix) ? (void *)net->W : then; };
     std::map<void *, size_t> current(arrays.begin(), arrays.end());
     for (const auto &a : cp.arrays) {
-        const auto it = current.find(a.first);
+        const auto it = current.find(now_at(a.first));
         if (it == current.end() || it->second != a.second.size())
             return fail(SNN_ERR_BAD_STATE, "the handle's structure changed since the checkpoint");
     }
     for (const auto &a : cp.arrays)
-        HIP_TRY(hipMemcpyAsync(a.first, a.second.data(), a.second.size(), hipMemcpyHostToDevice, net->stream), SNN_ERR_BUFFER_WRITE);
+        HIP_TRY(hipMemcpyAsync(now_at(a.first), a.second.data(), a.second.size(), hipMemcpyHostToDevice, net->stream), SNN_ERR_BUFFER_WRITE);
     HIP_TRY(hipStreamSynchronize(net->stream), SNN_ERR_WAIT);
     if (!cp.peak_rows.empty())
         HIP_TRY(copy_sync(net, net->pk_raster, cp.peak_rows.data(), cp.peak_rows.size() * 8, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);

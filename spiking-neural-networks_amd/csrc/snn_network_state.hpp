@@ -376,6 +376,11 @@ struct snn_network {
     bool w24_valid = false;                // the image holds W as it is now
     bool w24_refused = false;              // W as it is now cannot be encoded, or the image could not be allocated: not tried again until W changes
     bool w24_enabled = true;               // SNN_AMD_W24=0 (A/B runs) keeps the pass on W; read when the handle is created
+    // Region hand-over (ensure_w24): the image takes the allocation W's placement search chose -- the one region of the handle
+    // whose speed was measured -- and W moves to a fresh allocation of its size, which the registry then holds as W.
+    bool w24_in_region = false;            // `w24` IS W's first allocation (W-sized); W lives in the allocation it moved out to
+    bool w24_region_enabled = true;        // SNN_AMD_W24_REGION=0 (A/B runs): no hand-over; read when the handle is created
+    size_t w24_region_min = (size_t)1 << 30;      // smallest image handed over; SNN_AMD_W24_REGION_MIN=<bytes> lowers it (tests)
     float *xbuf = nullptr;
     float *part_i = nullptr, *part_t = nullptr;
     uint32_t *n_in = nullptr, *tcount = nullptr;
@@ -441,6 +446,7 @@ struct snn_network {
     struct Checkpoint {
         bool valid = false;
         hvec<std::pair<void *, hvec<uint8_t>>> arrays;
+        void *matrix = nullptr;                   // where W was when the checkpoint was taken (the region hand-over of ensure_w24 moves it)
         hvec<long long> st_clock;
         Cursors cur;
         CacheState cache;

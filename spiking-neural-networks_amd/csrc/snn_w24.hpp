@@ -45,6 +45,15 @@ SNN_W24_HD inline size_t w24_image_bytes(uint32_t n_rows, size_t ld)
 {
     return w24_row_units(n_rows) * (ld / W24_UNIT_COLS) * W24_UNIT_BYTES + W24_SLACK;
 }
+// Region hand-over (ensure_w24): the image may take over the allocation of the matrix it was packed from.  The body of W is its
+// rows padded to groups of four, 4 bytes per entry; W's own slack follows the body and is left out, so that the image -- its own
+// slack included -- never reaches into it.  3 bytes against 4 per entry, but rows padded to 16 against 4 and 48 KiB of slack:
+// false for matrices of few rows or few columns, whose padding and slack outweigh the quarter saved.
+SNN_W24_HD inline size_t w24_matrix_body_bytes(uint32_t n_rows, size_t ld) { return (((size_t)n_rows + 3) / 4) * 4 * ld * 4; }
+SNN_W24_HD inline bool w24_fits_matrix(uint32_t n_rows, size_t ld)
+{
+    return ld >= W24_UNIT_COLS && ld % W24_UNIT_COLS == 0 && w24_image_bytes(n_rows, ld) <= w24_matrix_body_bytes(n_rows, ld);
+}
 // byte offset of unit (row unit ru, column block cb)
 SNN_W24_HD inline size_t w24_unit_offset(size_t ru, size_t cb, size_t ld) { return (ru * (ld / W24_UNIT_COLS) + cb) * W24_UNIT_BYTES; }
 // byte offset of byte k (0 = least significant .. 2) of the code of (row p, column q); a code may straddle two planes
