@@ -196,8 +196,9 @@ int snn_fill_graph_synthetic(snn_network_t *net, uint64_t seed, float lo, float 
  * weight_rule, a non-finite w_lo / w_hi or, with SNN_WEIGHT_UNIFORM, a w_hi - w_lo that overflows -- NaN is the absent-edge
  * sentinel -- (SNN_ERR_BAD_ARG). */
 typedef enum { SNN_RULE_ALL = 0, SNN_RULE_CHEBYSHEV = 1, SNN_RULE_EUCLIDEAN = 2, SNN_RULE_SAME_POSITION = 3 } snn_connection_rule;
-/* (SNN_WEIGHT_DISPLACEMENT: snn_connect_by_spec / snn_connect_by_specs_csr only, below) */
-typedef enum { SNN_WEIGHT_CONSTANT = 0, SNN_WEIGHT_UNIFORM = 1, SNN_WEIGHT_DISPLACEMENT = 2 } snn_weight_rule;
+/* (SNN_WEIGHT_DISPLACEMENT: snn_connect_by_spec / snn_connect_by_specs_csr and the factors calls only; SNN_WEIGHT_FACTORS:
+ * snn_connect_by_factors / snn_connect_by_factors_csr only, below) */
+typedef enum { SNN_WEIGHT_CONSTANT = 0, SNN_WEIGHT_UNIFORM = 1, SNN_WEIGHT_DISPLACEMENT = 2, SNN_WEIGHT_FACTORS = 3 } snn_weight_rule;
 int snn_connect_by_rule(snn_network_t *net, uint32_t pre_id, uint32_t post_id, uint32_t rule, uint32_t extent,
                         int self_edges, float probability, uint64_t edge_seed, uint32_t weight_rule, float w_lo,
                         float w_hi, uint64_t weight_seed);
@@ -358,6 +359,42 @@ typedef struct snn_connect_spec {
 } snn_connect_spec;
 int snn_connect_by_spec(snn_network_t *net, const snn_connect_spec *spec);                           /* dense handles */
 int snn_connect_by_specs_csr(snn_network_t *net, const snn_connect_spec *specs, uint32_t n_specs);   /* sparse handles */
+
+/* Connect by rule with FACTORED weights: the two calls above with one more weight rule, for the weight form of the reference's
+ * associative-memory experiments -- the Hopfield matrix w[i][j] = scalar * sum_p (xi_p[i] - b)(xi_p[j] - a) with a zero diagonal and
+ * an edge where w != 0, and the cross-lattice weight that depends on the post position alone (get_weights / weights_ie of
+ * interface_gpu/experiments/pipeline_setup.py:44-64, used as exc_lattice.connect(lambda x, y: w[i(x)][i(y)] != 0, lambda x, y:
+ * w[i(x)][i(y)]) and network.connect(i1, e1, lambda x, y: True, lambda x, y: w_ie[pos(y)]) by bayesian_inference_pipeline*.py).
+ * Both are w(i, j) = scale * sum_p U[p][i] * V[p][j]: the Hopfield matrix with U = xi - b and V = xi - a, a per-post table with one
+ * factor, U = 1 and V = the table, a per-pre table its mirror -- O(P N) numbers where the matrix has O(N^2).
+ * `spec` has every field with the meaning it has in snn_connect_by_spec; with spec.record.weight_rule < SNN_WEIGHT_FACTORS the
+ * fields after it are not read and the two calls write, bit for bit, what snn_connect_by_spec / snn_connect_by_specs_csr write.
+ * With SNN_WEIGHT_FACTORS, for the pair (pre index i, post index j; lattice-local) IN BINARY64, as numpy computes it:
+ *   s = +0.0;  for p = 0 .. n_factors-1 ascending: s = s + (pre_factors[p][i] * post_factors[p][j])  -- the product rounded, then
+ *   the sum, no fused multiply-add;  w64 = s * scale;  the stored weight is (float)w64, round to nearest even.
+ * The pair is None where the rule, self_edges or the draw say so (as in snn_connect_by_spec: extent, probability, edge_seed, wrap,
+ * the pair index) or where drop_zero != 0 and w64 == 0.0 (the reference's `w != 0` predicate); otherwise Some(w), and Some(0.0f)
+ * is an edge when drop_zero == 0.  w_lo, w_hi, weight_seed and the table fields are not read.  The factor arrays are read during
+ * the call only (copied into device buffers that are freed before the call returns).
+ * snn_connect_by_factors_csr applies its n items in order and commits once, as snn_connect_by_specs_csr does: one call carries a
+ * Hopfield block together with the plain records of the same network; a factors item takes its candidates from its rule
+ * (SNN_RULE_ALL visits every presynaptic cell of every row).
+ * Refused as the calls above refuse, before anything changes and with SNN_ERR_BAD_ARG naming the argument ("item k: " first in
+ * the sparse form): a null pre_factors or post_factors, n_factors == 0 or > 65536, an entry of either array or a scale that is
+ * not finite, and n_factors * max|pre_factors| * max|post_factors| * |scale| (binary64) not below 2^127 -- a sufficient bound that
+ * no weight leaves binary32, found in O(P N).  Shard handles (post_factors is the FULL postsynaptic lattice there too), by-lattice
+ * shards, handles that are not finalized, reward-modulated handles and spike-train presynaptic lattices: as with the calls
+ * above.  All or nothing, as they are. */
+typedef struct snn_connect_factors {
+    snn_connect_spec spec;        /* record.weight_rule == SNN_WEIGHT_FACTORS selects the fields below */
+    uint32_t n_factors;           /* P >= 1 */
+    int32_t  drop_zero;           /* != 0: a pair whose binary64 weight compares equal to 0 is None */
+    double   scale;
+    const double *pre_factors;    /* host, [n_factors][cell count of the pre lattice], lattice-local index */
+    const double *post_factors;   /* host, [n_factors][cell count of the post lattice] -- full lattice, also on a shard */
+} snn_connect_factors;
+int snn_connect_by_factors(snn_network_t *net, const snn_connect_factors *f);                          /* dense handles  */
+int snn_connect_by_factors_csr(snn_network_t *net, const snn_connect_factors *items, uint32_t n);      /* sparse handles */
 
 /* ---- switches (Lattice / LatticeNetwork pub fields, neuron/mod.rs:570-586, 1577-1588) -- */
 

@@ -148,6 +148,12 @@ class ConnectSpec(C.Structure):
                 ("table", C.POINTER(C.c_float))]
 
 
+class ConnectFactors(C.Structure):
+    """snn_connect_factors of include/snn_amd.h (snn_connect_by_factors, snn_connect_by_factors_csr)"""
+    _fields_ = [("spec", ConnectSpec), ("n_factors", C.c_uint32), ("drop_zero", C.c_int32), ("scale", C.c_double),
+                ("pre_factors", C.POINTER(C.c_double)), ("post_factors", C.POINTER(C.c_double))]
+
+
 EXCHANGE_ALLGATHER, EXCHANGE_HALO = 0, 1
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)      # snn_exchange_fn(user, hip_stream)
@@ -169,6 +175,7 @@ u32p = C.POINTER(C.c_uint32)
 i32p = C.POINTER(C.c_int32)
 u8p = C.POINTER(C.c_uint8)
 u64p = C.POINTER(C.c_uint64)
+f64p = C.POINTER(C.c_double)
 H = C.c_void_p   # snn_network_t*
 
 # name -> (restype, argtypes); kept in one place so tests can check it against the header
@@ -205,6 +212,7 @@ SIGNATURES = {
     "snn_connect_by_rule": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_uint64,
                                       C.c_uint32, C.c_float, C.c_float, C.c_uint64]),
     "snn_connect_by_spec": (C.c_int, [H, C.POINTER(ConnectSpec)]),
+    "snn_connect_by_factors": (C.c_int, [H, C.POINTER(ConnectFactors)]),
     "snn_graph_lookup": (C.c_int, [H, u32p, u32p, C.c_size_t, f32p, u8p]),
     "snn_graph_edit": (C.c_int, [H, u32p, u32p, f32p, u8p, C.c_size_t]),
     "snn_graph_incoming": (C.c_int, [H, C.c_uint32, u32p, f32p, C.c_uint64, u64p]),
@@ -221,6 +229,7 @@ SIGNATURES = {
     "snn_graph_csr_outgoing": (C.c_int, [H, C.c_uint32, u32p, f32p, C.c_uint64, u64p]),
     "snn_connect_by_rules_csr": (C.c_int, [H, C.POINTER(ConnectRecord), C.c_uint32]),
     "snn_connect_by_specs_csr": (C.c_int, [H, C.POINTER(ConnectSpec), C.c_uint32]),
+    "snn_connect_by_factors_csr": (C.c_int, [H, C.POINTER(ConnectFactors), C.c_uint32]),
     "snn_set_synapses": (C.c_int, [H, C.c_int, C.c_int]),
     "snn_set_plasticity": (C.c_int, [H, C.c_uint32] + [C.c_float] * 5 + [C.c_int]),
     "snn_set_history": (C.c_int, [H, C.c_int, C.c_int]),

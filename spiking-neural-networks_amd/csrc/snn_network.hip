@@ -328,6 +328,12 @@ int snn_connect_by_spec(snn_network_t *net, const snn_connect_spec *spec) ABI_TR
     return connect_dense(net, *spec, CONNECT_SPEC_WEIGHTS);
 }
 ABI_CATCH
+int snn_connect_by_factors(snn_network_t *net, const snn_connect_factors *f) ABI_TRY
+{
+    if (!f) return fail(SNN_ERR_BAD_ARG, "f is null");
+    return connect_dense(net, f->spec, CONNECT_FACTOR_WEIGHTS, f);
+}
+ABI_CATCH
 // the Graph trait (graph/mod.rs:42-72) on a dense handle ...
 int snn_graph_lookup(snn_network_t *net, const uint32_t *pre, const uint32_t *post, size_t n, float *weights, uint8_t *connected) ABI_TRY
 { return graph_lookup(net, false, pre, post, n, weights, connected); }
@@ -434,6 +440,9 @@ int snn_connect_by_rules_csr(snn_network_t *net, const snn_connect_record *recor
 ABI_CATCH
 int snn_connect_by_specs_csr(snn_network_t *net, const snn_connect_spec *specs, uint32_t n_specs) ABI_TRY
 { return connect_csr(net, nullptr, specs, n_specs); }
+ABI_CATCH
+int snn_connect_by_factors_csr(snn_network_t *net, const snn_connect_factors *items, uint32_t n) ABI_TRY
+{ return connect_csr(net, nullptr, nullptr, n, items, true); }
 ABI_CATCH
 
 int snn_set_synapses(snn_network_t *net, int electrical_synapse, int chemical_synapse) ABI_TRY

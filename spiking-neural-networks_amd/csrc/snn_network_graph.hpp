@@ -86,7 +86,7 @@ int connect_check(const snn_network *net, const std::string &where, const snn_co
     if (r.weight_rule >= weight_rules) return fail(SNN_ERR_BAD_ARG, where + "weight_rule: unknown weight rule " + std::to_string(r.weight_rule));
     if (r.probability != r.probability) return fail(SNN_ERR_BAD_ARG, where + "probability is NaN");
     *pre_out = pre; *post_out = post;
-    if (r.weight_rule == CONNECT_DISPLACEMENT) return SNN_OK;      // (w_lo, w_hi are not read)
+    if (r.weight_rule == CONNECT_DISPLACEMENT || r.weight_rule == CONNECT_FACTORS) return SNN_OK;      // (w_lo, w_hi are not read)
     if (r.w_lo - r.w_lo != 0.0f) return fail(SNN_ERR_BAD_ARG, where + "w_lo is not finite (NaN is the absent-edge sentinel of the device matrix)");
     if (r.w_hi - r.w_hi != 0.0f) return fail(SNN_ERR_BAD_ARG, where + "w_hi is not finite (NaN is the absent-edge sentinel of the device matrix)");
     if (r.weight_rule == CONNECT_UNIFORM && (r.w_hi - r.w_lo) - (r.w_hi - r.w_lo) != 0.0f)      // (lo + inf * u24 is +-inf, or NaN where u24 is 0)
@@ -97,10 +97,10 @@ int connect_check(const snn_network *net, const std::string &where, const snn_co
 // what a spec adds to connect_check: the wrap flags, and for SNN_WEIGHT_DISPLACEMENT the table -- its dimensions follow from the
 // two grids and the flags, and every entry is finite or NaN (None).  `ext`: the kernels' form of it, the table still on the host.
 int connect_spec_check(const snn_network *net, const std::string &where, const snn_connect_spec &s, const LatticeInfo **pre_out,
-                              const LatticeInfo **post_out, ConnectSpecExt *ext)
+                              const LatticeInfo **post_out, ConnectSpecExt *ext, uint32_t weight_rules = CONNECT_SPEC_WEIGHTS)
 {
     const snn_connect_record &r = s.record;
-    TRY(connect_check(net, where, r, CONNECT_SPEC_WEIGHTS, pre_out, post_out));
+    TRY(connect_check(net, where, r, weight_rules, pre_out, post_out));
     if (s.wrap > (SNN_WRAP_ROWS | SNN_WRAP_COLS)) return fail(SNN_ERR_BAD_ARG, where + "wrap: unknown flags " + std::to_string(s.wrap));
     const LatticeInfo *pre = *pre_out, *post = *post_out;
     *ext = ConnectSpecExt{};
@@ -134,6 +134,50 @@ int connect_spec_upload(snn_network *net, const snn_connect_spec &s, ConnectSpec
     return SNN_OK;
 }
 
+// what snn_connect_by_factors adds to connect_spec_check, for a record with SNN_WEIGHT_FACTORS (with another weight rule nothing of
+// it is read): the factor count, both arrays finite and the bound that keeps every weight inside binary32 --
+// |w64| <= n_factors * max|U| * max|V| * |scale| up to rounding, far below the 2^128 a conversion would need to overflow.
+int connect_factors_check(const std::string &where, const snn_connect_factors &f, const LatticeInfo *pre, const LatticeInfo *post)
+{
+    if (f.spec.record.weight_rule != CONNECT_FACTORS) return SNN_OK;
+    if (f.n_factors == 0 || f.n_factors > 65536u)
+        return fail(SNN_ERR_BAD_ARG, where + "n_factors: " + std::to_string(f.n_factors) + " given, a factors record takes 1 .. 65536");
+    if (!f.pre_factors) return fail(SNN_ERR_BAD_ARG, where + "pre_factors is null: SNN_WEIGHT_FACTORS reads its weights from it");
+    if (!f.post_factors) return fail(SNN_ERR_BAD_ARG, where + "post_factors is null: SNN_WEIGHT_FACTORS reads its weights from it");
+    if (f.scale - f.scale != 0.0) return fail(SNN_ERR_BAD_ARG, where + "scale is not finite");
+    double largest[2] = {0.0, 0.0};
+    const double *arrays[2] = {f.pre_factors, f.post_factors};
+    const size_t counts[2] = {(size_t)f.n_factors * pre->count, (size_t)f.n_factors * post->count};
+    for (int s = 0; s < 2; ++s)
+        for (size_t k = 0; k < counts[s]; ++k) {
+            const double v = arrays[s][k];
+            if (v - v != 0.0)
+                return fail(SNN_ERR_BAD_ARG, where + (s ? "post_factors" : "pre_factors") + ": entry " + std::to_string(k) + " is not finite");
+            largest[s] = std::max(largest[s], std::fabs(v));
+        }
+    const double bound = (double)f.n_factors * largest[0] * largest[1] * std::fabs(f.scale);
+    if (!(bound < 0x1p127))
+        return fail(SNN_ERR_BAD_ARG, where + "scale: n_factors * max|pre_factors| * max|post_factors| * |scale| is not below 2^127: a weight "
+                                             "could leave binary32");
+    return SNN_OK;
+}
+
+// the factor arrays of a checked factors record in device buffers of the handle's allocator (the caller's dev_ptrs free them)
+int connect_factors_upload(snn_network *net, const snn_connect_factors &f, const LatticeInfo *pre, const LatticeInfo *post,
+                           ConnectFactorsExt *ext, dev_ptr<double> *pre_d, dev_ptr<double> *post_d)
+{
+    *ext = ConnectFactorsExt{};
+    if (f.spec.record.weight_rule != CONNECT_FACTORS) return SNN_OK;
+    const size_t pre_bytes = (size_t)f.n_factors * pre->count * 8, post_bytes = (size_t)f.n_factors * post->count * 8;
+    HIP_TRY(snn_malloc(pre_d, std::max<size_t>(pre_bytes, 256)), SNN_ERR_BUFFER_CREATE);
+    HIP_TRY(snn_malloc(post_d, std::max<size_t>(post_bytes, 256)), SNN_ERR_BUFFER_CREATE);
+    if (pre_bytes) HIP_TRY(copy_sync(net, pre_d->get(), f.pre_factors, pre_bytes, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+    if (post_bytes) HIP_TRY(copy_sync(net, post_d->get(), f.post_factors, post_bytes, hipMemcpyHostToDevice), SNN_ERR_BUFFER_WRITE);
+    ext->U = pre_d->get(); ext->V = post_d->get();
+    ext->n_factors = f.n_factors; ext->drop_zero = f.drop_zero != 0; ext->scale = f.scale;
+    return SNN_OK;
+}
+
 // one record as the kernels take it: all of lattice `pre`, the columns (rows of a sparse graph) [c_begin, c_end) of lattice `post`
 ConnectArgs connect_args(const snn_network *net, const snn_connect_record &r, const LatticeInfo *pre, const LatticeInfo *post, uint32_t c_begin,
                          uint32_t c_end)
@@ -147,8 +191,9 @@ ConnectArgs connect_args(const snn_network *net, const snn_connect_record &r, co
     return a;
 }
 
-// snn_connect_by_rule and snn_connect_by_spec: one body.  A plain spec (no table, no distance on a ring) launches k_connect_rule.
-int connect_dense(snn_network_t *net, const snn_connect_spec &s, uint32_t weight_rules)
+// snn_connect_by_rule, snn_connect_by_spec and snn_connect_by_factors (`factors` set: s is its spec): one body.  A plain spec (no
+// table, no distance on a ring) launches k_connect_rule, a factors record k_connect_factors.
+int connect_dense(snn_network_t *net, const snn_connect_spec &s, uint32_t weight_rules, const snn_connect_factors *factors = nullptr)
 {
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
     if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
@@ -159,11 +204,15 @@ int connect_dense(snn_network_t *net, const snn_connect_spec &s, uint32_t weight
     if (weight_rules == CONNECT_RULE_WEIGHTS)
         TRY(connect_check(net, "", r, CONNECT_RULE_WEIGHTS, &pre, &post));
     else
-        TRY(connect_spec_check(net, "", s, &pre, &post, &x));
+        TRY(connect_spec_check(net, "", s, &pre, &post, &x, weight_rules));
+    if (factors) TRY(connect_factors_check("", *factors, pre, post));
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
     TRY(end_run(net));                     // a deferred reward-modulated update belongs to the OLD weights: apply it first
     dev_ptr<float> table_d;                // (freed when the call returns; a failure here leaves the graph as it was)
     TRY(connect_spec_upload(net, s, &x, &table_d));
+    dev_ptr<double> pre_factors_d, post_factors_d;
+    ConnectFactorsExt fx{};
+    if (factors) TRY(connect_factors_upload(net, *factors, pre, post, &fx, &pre_factors_d, &post_factors_d));
     net->cross_checked = false;
     net->cache.counts_dirty = true;        // stale from here on, whichever way the call ends (as graph_rows_io marks them on every exit of a set)
     w24_invalidate(net);
@@ -177,7 +226,13 @@ int connect_dense(snn_network_t *net, const snn_connect_spec &s, uint32_t weight
         const dim3 grid(blocks_x, std::min<uint32_t>(groups, 4096));
         const bool thin = r.probability < 1.0f, self = r.self_edges != 0, wrap = x.period_r || x.period_c;
         // (probability <= 0: the draw is made and never succeeds)
-        if (connect_spec_is_plain((int)r.rule, (int)r.weight_rule, wrap))
+        if (r.weight_rule == CONNECT_FACTORS) {
+            // row tiles in y: enough workgroups to fill the device, each walking many tiles with the V tile it staged once
+            a.w_lo = 0.0f;                 // (connect_factors_on asks connect_spec_value for a constant: 0 or None)
+            const uint32_t tiles = (groups + 3u) / 4u;
+            const dim3 grid_f(blocks_x, std::min<uint32_t>(tiles, std::max<uint32_t>(1u, 8192u / blocks_x)));
+            hipLaunchKernelGGL(connect_factors_kernel((int)r.rule, thin, self), grid_f, dim3(256), 0, net->stream, ConnectFactorsArgs{a, x, fx});
+        } else if (connect_spec_is_plain((int)r.rule, (int)r.weight_rule, wrap))
             hipLaunchKernelGGL(connect_kernel((int)r.rule, (int)r.weight_rule, thin, self), grid, dim3(256), 0, net->stream, a);
         else
             hipLaunchKernelGGL(connect_spec_kernel((int)r.rule, (int)r.weight_rule, wrap, thin, self), grid, dim3(256), 0, net->stream,
@@ -684,20 +739,26 @@ int commit_device_csr(snn_network *net, dev_ptr<uint32_t> &ptr_d, dev_ptr<uint32
     return rc;
 }
 
-// snn_connect_by_rules_csr (specs == nullptr: every record plain) and snn_connect_by_specs_csr (records == nullptr): one body
-int connect_csr(snn_network_t *net, const snn_connect_record *records, const snn_connect_spec *specs, uint32_t n_records)
+// snn_connect_by_rules_csr (specs == nullptr: every record plain), snn_connect_by_specs_csr (records == nullptr) and
+// snn_connect_by_factors_csr (factors_form: the list is `items`, the spec of record k is items[k].spec): one body
+int connect_csr(snn_network_t *net, const snn_connect_record *records, const snn_connect_spec *specs, uint32_t n_records,
+                const snn_connect_factors *items = nullptr, bool factors_form = false)
 {
     if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
     if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
     if (!net->csr) return fail(SNN_ERR_BAD_STATE, "handle holds a dense graph: connect it with snn_connect_by_rule");
     if (net->block_mode) return fail(SNN_ERR_BAD_STATE, "connecting by rule does not cover shards by lattice (range-set ownership): not covered");
     if (n_records == 0) return SNN_OK;
-    if (!records && !specs) return fail(SNN_ERR_BAD_ARG, "records is null");
+    if (!records && !specs && !items) return fail(SNN_ERR_BAD_ARG, factors_form ? "items is null" : "records is null");
+    auto spec_of = [&](uint32_t k) -> const snn_connect_spec & { return items ? items[k].spec : specs[k]; };
     hvec<std::pair<const LatticeInfo *, const LatticeInfo *>> ends(n_records);
     hvec<ConnectSpecExt> exts(n_records);
     for (uint32_t k = 0; k < n_records; ++k) {
-        const std::string where = "record " + std::to_string(k) + ": ";
-        if (specs) TRY(connect_spec_check(net, where, specs[k], &ends[k].first, &ends[k].second, &exts[k]));
+        const std::string where = (factors_form ? "item " : "record ") + std::to_string(k) + ": ";
+        if (items) {
+            TRY(connect_spec_check(net, where, items[k].spec, &ends[k].first, &ends[k].second, &exts[k], CONNECT_FACTOR_WEIGHTS));
+            TRY(connect_factors_check(where, items[k], ends[k].first, ends[k].second));
+        } else if (specs) TRY(connect_spec_check(net, where, specs[k], &ends[k].first, &ends[k].second, &exts[k]));
         else TRY(connect_check(net, where, records[k], CONNECT_RULE_WEIGHTS, &ends[k].first, &ends[k].second));
     }
     HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
@@ -730,7 +791,7 @@ int connect_csr(snn_network_t *net, const snn_connect_record *records, const snn
     }
     // ---- record by record: count, scan, check the total, fill, swap ----
     for (uint32_t k = 0; k < n_records; ++k) {
-        const snn_connect_record &r = specs ? specs[k].record : records[k];
+        const snn_connect_record &r = records ? records[k] : spec_of(k).record;
         const LatticeInfo *lp = ends[k].first, *lq = ends[k].second;
         // the block's rows this handle owns, as local rows (the dense form: its columns)
         const uint32_t c_begin = std::max(lq->first, net->q0), c_end = std::min(lq->first + lq->count, net->q0 + n);
@@ -745,9 +806,17 @@ int connect_csr(snn_network_t *net, const snn_connect_record *records, const snn
         const bool thin = r.probability < 1.0f, self = r.self_edges != 0, wrap = exts[k].period_r || exts[k].period_c;
         const bool plain = connect_spec_is_plain((int)r.rule, (int)r.weight_rule, wrap);
         dev_ptr<float> table_d;                        // (read by both passes; freed after the wait that ends this record)
-        if (specs) TRY(connect_spec_upload(net, specs[k], &exts[k], &table_d));
+        if (!records) TRY(connect_spec_upload(net, spec_of(k), &exts[k], &table_d));
+        dev_ptr<double> pre_factors_d, post_factors_d;     // (likewise)
+        ConnectFactorsExt fx{};
+        if (items) TRY(connect_factors_upload(net, items[k], lp, lq, &fx, &pre_factors_d, &post_factors_d));
+        const bool by_factors = r.weight_rule == CONNECT_FACTORS;
+        if (by_factors) a.c.w_lo = 0.0f;               // (connect_factors_on asks connect_spec_value for a constant: 0 or None)
         const dim3 grid(std::min<uint32_t>((n + 3u) / 4u, 16384u));
-        if (plain)
+        if (by_factors)
+            hipLaunchKernelGGL(connect_csr_factors_kernel<false>((int)r.rule, thin, self), grid, dim3(256), 0, net->stream,
+                               ConnectCsrFactorsArgs{a, exts[k], fx});
+        else if (plain)
             hipLaunchKernelGGL(connect_csr_kernel<false>((int)r.rule, (int)r.weight_rule, thin, self), grid, dim3(256), 0, net->stream, a);
         else
             hipLaunchKernelGGL(connect_csr_spec_kernel<false>((int)r.rule, (int)r.weight_rule, wrap, thin, self), grid, dim3(256), 0, net->stream,
@@ -756,12 +825,15 @@ int connect_csr(snn_network_t *net, const snn_connect_record *records, const snn
         uint64_t total = 0;
         TRY(device_scan(net, len_d, ptr[cur ^ 1], n, sums_d, &total));     // lengths -> n + 1 offsets
         if (total >= 0xFFFFFFFFull)
-            return fail(SNN_ERR_DIM_MISMATCH, "record " + std::to_string(k) + ": the graph would hold " + std::to_string(total) +
+            return fail(SNN_ERR_DIM_MISMATCH, (factors_form ? "item " : "record ") + std::to_string(k) + ": the graph would hold " + std::to_string(total) +
                                                   " stored synapses, more than 2^32-2 per handle");
         TRY(sized(&pre[cur ^ 1], total * 4));
         TRY(sized(&w[cur ^ 1], total * 4));
         a.new_ptr = ptr[cur ^ 1]; a.new_pre = pre[cur ^ 1]; a.new_w = w[cur ^ 1];
-        if (plain)
+        if (by_factors)
+            hipLaunchKernelGGL(connect_csr_factors_kernel<true>((int)r.rule, thin, self), grid, dim3(256), 0, net->stream,
+                               ConnectCsrFactorsArgs{a, exts[k], fx});
+        else if (plain)
             hipLaunchKernelGGL(connect_csr_kernel<true>((int)r.rule, (int)r.weight_rule, thin, self), grid, dim3(256), 0, net->stream, a);
         else
             hipLaunchKernelGGL(connect_csr_spec_kernel<true>((int)r.rule, (int)r.weight_rule, wrap, thin, self), grid, dim3(256), 0, net->stream,

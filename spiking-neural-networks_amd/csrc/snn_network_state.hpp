@@ -23,6 +23,7 @@
 #include "../../include/snn_amd.h"
 #include "snn_kernels_connect.hpp"
 #include "snn_kernels_connect_csr.hpp"
+#include "snn_kernels_connect_factors.hpp"
 #include "snn_kernels_csr.hpp"
 #include "snn_kernels_dense_step.hpp"
 #include "snn_kernels_edge_history.hpp"

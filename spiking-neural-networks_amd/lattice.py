@@ -18,10 +18,10 @@ from .network import (CUSTOM, NT_CUSTOM, RC_CUSTOM, REFRACTORINESS_CUSTOM, ST_CU
                       DeviceNetwork, HODGKIN_HUXLEY, IZHIKEVICH, LIF, QUADRATIC_INTEGRATE_AND_FIRE, SIMPLE_LIF,
                       ADAPTIVE_LIF, ADAPTIVE_EXP_LIF, LEAKY_IZHIKEVICH,
                       NT_APPROXIMATE, NT_DESTEXHE,
-                      RC_APPROXIMATE, RC_DESTEXHE, ST_NONE, ST_POISSON, ST_RATE, ConnectionRule, WeightRule, check_rule_pair, rule_pairs)
+                      RC_APPROXIMATE, RC_DESTEXHE, ST_NONE, ST_POISSON, ST_RATE, ConnectionRule, WeightRule, WEIGHT_FACTORS, check_rule_pair, rule_pairs)
 
 
-def _rule_records(rule, weight):
+def _rule_records(rule, weight, shapes=None):
     """(ConnectionRule, WeightRule) when connect(...) was handed records; None when the arguments are the reference's two closures"""
     if not isinstance(rule, ConnectionRule):
         if isinstance(weight, WeightRule):
@@ -31,6 +31,8 @@ def _rule_records(rule, weight):
         raise TypeError("a ConnectionRule goes with a WeightRule (or None: every edge weighs 1), not with a closure")
     weight = WeightRule.constant(1.0) if weight is None else weight
     check_rule_pair(rule, weight)
+    if shapes is not None and weight.kind == WEIGHT_FACTORS:       # its factor lengths fit the two grids, or ValueError -- here, not at the upload
+        weight.factor_arrays(*shapes)
     return rule, weight
 
 
@@ -617,7 +619,7 @@ class Lattice:
         """two closures on positions as in the reference, or a ConnectionRule and a WeightRule (the graph the device call
         DeviceNetwork.connect_by_rule produces, without a Python call per pair).  Records replace the whole graph, so the last
         one IS the graph: nothing of size N^2 is built until `weights` / `connections` are read"""
-        records = _rule_records(connection_conditional, weight_logic)
+        records = _rule_records(connection_conditional, weight_logic, ((self.rows, self.cols),) * 2)
         if records is not None:
             self._weights = self._connections = None
             self._rule = records
@@ -885,7 +887,7 @@ class LatticeNetwork:
         pre = self.lattices.get(presynaptic_id) or self.spike_train_lattices[presynaptic_id]
         post = self.lattices[postsynaptic_id]
         key = (presynaptic_id, postsynaptic_id)
-        records = _rule_records(connection_conditional, weight_logic)
+        records = _rule_records(connection_conditional, weight_logic, ((pre.rows, pre.cols), (post.rows, post.cols)))
         if records is not None and self.hold_connecting_rules:
             # the record IS the block: its dict entries go, both lattices' nodes join the connecting graph as _connect_graph adds them
             if self.connecting:

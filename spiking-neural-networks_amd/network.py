@@ -43,7 +43,7 @@ def _out(shape, dtype=np.float32):
 _PTR = {"f32": _lib.f32p, "u32": _lib.u32p, "i32": _lib.i32p}
 
 RULE_ALL, RULE_CHEBYSHEV, RULE_EUCLIDEAN, RULE_SAME_POSITION = 0, 1, 2, 3      # snn_connection_rule
-WEIGHT_CONSTANT, WEIGHT_UNIFORM, WEIGHT_DISPLACEMENT = 0, 1, 2                  # snn_weight_rule
+WEIGHT_CONSTANT, WEIGHT_UNIFORM, WEIGHT_DISPLACEMENT, WEIGHT_FACTORS = 0, 1, 2, 3    # snn_weight_rule
 WRAP_ROWS, WRAP_COLS = 1, 2                                                    # snn_connect_spec.wrap
 
 
@@ -166,10 +166,14 @@ class WeightRule:
     lo + (hi - lo) * u24(hash(seed, idx)) in float32 -- synthetic.uniform on the pair index -- or
     WeightRule.displacement(table, wrap): the entry of a 2-D float32 table for the displacement post - pre (a convolution kernel;
     on a ring or torus with wrap), NaN where that displacement carries no edge.  The table's shape follows from the two grids:
-    per dimension max(pre, post) where it wraps, pre + post - 1 where it does not (SNN_WEIGHT_DISPLACEMENT of include/snn_amd.h)."""
+    per dimension max(pre, post) where it wraps, pre + post - 1 where it does not (SNN_WEIGHT_DISPLACEMENT of include/snn_amd.h).
+    WeightRule.factors(U, V, scale, drop_zero): w(i, j) = scale * sum_p U[p][i] * V[p][j] in float64, patterns added in order
+    (SNN_WEIGHT_FACTORS) -- WeightRule.hopfield(patterns, a, b, scalar) is the reference's auto-associative matrix (U = patterns - b,
+    V = patterns - a, an edge where w != 0), WeightRule.per_post(table) / per_pre(table) a weight that depends on one position only."""
 
-    def __init__(self, kind, lo=0.0, hi=0.0, seed=0, table=None, wrap=False):
-        if kind not in (WEIGHT_CONSTANT, WEIGHT_UNIFORM, WEIGHT_DISPLACEMENT):
+    def __init__(self, kind, lo=0.0, hi=0.0, seed=0, table=None, wrap=False, _factors=None):
+        # (WEIGHT_FACTORS comes from WeightRule.factors, which has checked its arrays: _factors = (U, V, scale, drop_zero))
+        if kind not in (WEIGHT_CONSTANT, WEIGHT_UNIFORM, WEIGHT_DISPLACEMENT) and not (kind == WEIGHT_FACTORS and _factors is not None):
             raise ValueError(f"unknown weight rule {kind!r}")
         if not (np.isfinite(np.float32(lo)) and np.isfinite(np.float32(hi))):
             raise ValueError("weights must be finite (NaN marks the absent edge)")
@@ -181,6 +185,7 @@ class WeightRule:
             raise ValueError("seed is a uint64")
         self.kind, self.lo, self.hi, self.seed = int(kind), float(lo), float(hi), int(seed)
         self.table, self.wrap = None, _wrap_flags(wrap)
+        self.pre_factors, self.post_factors, self.scale, self.drop_zero = _factors or (None, None, 1.0, False)      # WEIGHT_FACTORS
         if kind == WEIGHT_DISPLACEMENT:
             table = np.ascontiguousarray(table, dtype=np.float32)
             if table.ndim != 2:
@@ -202,6 +207,61 @@ class WeightRule:
     @classmethod
     def displacement(cls, table, wrap=False):
         return cls(WEIGHT_DISPLACEMENT, table=table, wrap=wrap)
+
+    @classmethod
+    def factors(cls, pre_factors, post_factors, scale=1.0, drop_zero=False):
+        """w(i, j) = scale * sum_p pre_factors[p][i] * post_factors[p][j]: float64 arrays [P, cells of the pre lattice] and
+        [P, cells of the post lattice] (one row: [cells]), lattice-local row-major index.  drop_zero: a pair whose float64 weight
+        is 0 has no edge (the reference's `w != 0` predicate); without it such a pair is an edge of weight 0."""
+        u = np.atleast_2d(np.ascontiguousarray(pre_factors, dtype=np.float64))
+        v = np.atleast_2d(np.ascontiguousarray(post_factors, dtype=np.float64))
+        if u.ndim != 2 or v.ndim != 2:
+            raise ValueError("factors are [P, cells] arrays")
+        if u.shape[0] != v.shape[0]:
+            raise ValueError(f"{u.shape[0]} pre factors and {v.shape[0]} post factors: one of each per term of the sum")
+        if not 1 <= u.shape[0] <= 65536:
+            raise ValueError(f"a factors rule takes 1 .. 65536 factors, not {u.shape[0]}")
+        scale = float(scale)
+        if not (np.isfinite(u).all() and np.isfinite(v).all() and np.isfinite(scale)):
+            raise ValueError("factors and scale must be finite")
+        # the device call's sufficient bound that no weight leaves float32, in float64 as it computes it
+        bound = np.float64(u.shape[0]) * (np.abs(u).max() if u.size else 0.0) * (np.abs(v).max() if v.size else 0.0) * abs(scale)
+        if not bound < 2.0 ** 127:
+            raise ValueError("n_factors * max|pre_factors| * max|post_factors| * |scale| is not below 2^127: a weight could overflow float32")
+        return cls(WEIGHT_FACTORS, _factors=(np.ascontiguousarray(u), np.ascontiguousarray(v), scale, bool(drop_zero)))
+
+    @classmethod
+    def hopfield(cls, patterns, a=0.0, b=0.0, scalar=1.0, drop_zero=True):
+        """the reference's get_weights(n, patterns, a, b, scalar) as a rule: w[i][j] = scalar * sum_p (xi_p[i] - b)(xi_p[j] - a), an
+        edge where w != 0; the zero diagonal is the connection rule's self_edges=False"""
+        xi = np.atleast_2d(np.asarray(patterns, dtype=np.float64))
+        return cls.factors(xi - np.float64(b), xi - np.float64(a), scalar, drop_zero)
+
+    @classmethod
+    def per_post(cls, table):
+        """a weight that depends on the post position only (connect(..., lambda x, y: w[pos(y)])): one factor, the pre side all ones.
+        The pre lattice's size is taken from the grids the rule is used on."""
+        rule = cls.factors(np.ones((1, 1)), np.asarray(table, dtype=np.float64).reshape(1, -1))
+        rule.pre_factors = None
+        return rule
+
+    @classmethod
+    def per_pre(cls, table):
+        """the mirror: a weight that depends on the pre position only"""
+        rule = cls.factors(np.asarray(table, dtype=np.float64).reshape(1, -1), np.ones((1, 1)))
+        rule.post_factors = None
+        return rule
+
+    def factor_arrays(self, pre_shape, post_shape):
+        """(pre_factors [P, n_pre], post_factors [P, n_post]) of a factors rule on two grids -- the all-ones side of per_post /
+        per_pre sized here -- or ValueError when the factor lengths do not match the grids"""
+        n_pre, n_post = int(pre_shape[0]) * int(pre_shape[1]), int(post_shape[0]) * int(post_shape[1])
+        u = np.ones((1, n_pre)) if self.pre_factors is None else self.pre_factors
+        v = np.ones((1, n_post)) if self.post_factors is None else self.post_factors
+        if u.shape[1] != n_pre or v.shape[1] != n_post:
+            raise ValueError(f"factors of {u.shape[1]} pre and {v.shape[1]} post cells do not fit grids {tuple(pre_shape)} -> {tuple(post_shape)} "
+                             f"of {n_pre} and {n_post} cells")
+        return u, v
 
     @staticmethod
     def table_shape(pre_shape, post_shape, wrap=False):
@@ -232,14 +292,30 @@ class WeightRule:
         return cls.displacement(table, wrap)
 
     def __repr__(self):
+        if self.kind == WEIGHT_FACTORS:
+            shape = lambda f: "ones" if f is None else f.shape
+            return (f"WeightRule(kind={self.kind}, pre_factors={shape(self.pre_factors)}, post_factors={shape(self.post_factors)}, "
+                    f"scale={self.scale}, drop_zero={self.drop_zero})")
         if self.kind == WEIGHT_DISPLACEMENT:
             return f"WeightRule(kind={self.kind}, table={self.table.shape}, wrap={_wrap_pair(self.wrap)})"
         return f"WeightRule(kind={self.kind}, lo={self.lo}, hi={self.hi}, seed={self.seed})"
 
     def values(self, pre_shape, post_shape, pre_index=None, post_index=None):
-        """float32[n_pre, n_post]: the weight the device call gives each pair (whether or not the rule connects it; NaN where the
-        displacement table says None); with pre_index / post_index (lattice-local indices) those rows / columns of it only"""
+        """[n_pre, n_post]: the weight the device call gives each pair (whether or not the rule connects it) -- float32, NaN where a
+        displacement table says None; float64 for a factors rule; with pre_index / post_index (lattice-local indices) those rows /
+        columns of it only.  A factors rule: the FLOAT64 weight w64 of include/snn_amd.h (the device stores its float32 rounding), NaN where drop_zero
+        drops the pair -- one `s = s + U[p][:, None] * V[p][None, :]` per factor, in order: O(P) per pair asked for"""
         ra, ca, rb, cb, idx = _pair_grid(pre_shape, post_shape, pre_index, post_index)
+        if self.kind == WEIGHT_FACTORS:
+            u, v = self.factor_arrays(pre_shape, post_shape)
+            i, j = (ra * max(pre_shape[1], 1) + ca).reshape(-1), (rb * max(post_shape[1], 1) + cb).reshape(-1)
+            total = np.zeros((i.size, j.size), np.float64)
+            for p in range(u.shape[0]):
+                total = total + u[p][i][:, None] * v[p][j][None, :]
+            total = total * np.float64(self.scale)
+            if self.drop_zero:
+                total[total == 0.0] = np.nan
+            return total
         if self.kind == WEIGHT_DISPLACEMENT:
             if self.table.shape != self.table_shape(pre_shape, post_shape, _wrap_pair(self.wrap)):
                 raise ValueError(f"a displacement table of shape {self.table.shape} does not fit grids {tuple(pre_shape)} -> {tuple(post_shape)}: "
@@ -262,7 +338,8 @@ def check_rule_pair(rule, weight):
 
 def rule_pairs(rule, weight, pre_shape, post_shape, pre_index=None, post_index=None):
     """(connected bool, weights float32, 0 where there is no edge) [n_pre, n_post]: the graph one connect record writes on the
-    device, from the records' host twins -- a NaN of the displacement table is an absent edge"""
+    device, from the records' host twins -- a NaN of the weight twin (a None of the displacement table, a pair that drop_zero of a
+    factors rule drops) is an absent edge; a factors rule's float64 weights are rounded to float32 here, as the device stores them"""
     check_rule_pair(rule, weight)
     on, w = rule.mask(pre_shape, post_shape, pre_index, post_index), weight.values(pre_shape, post_shape, pre_index, post_index)
     on = on & ~np.isnan(w)
@@ -486,6 +563,25 @@ class DeviceNetwork:
     def fill_graph_synthetic(self, seed, lo, hi, with_diagonal=False):
         self._check(self._L.snn_fill_graph_synthetic(self._h, seed, lo, hi, int(with_diagonal)))
 
+    def _lattice_shape(self, lattice_id):
+        """(rows, cols) of a lattice of this handle, None for an id it does not know (the device call names it)"""
+        shape = self.lattices.get(int(lattice_id))
+        return None if shape is None else tuple(shape[:2])
+
+    def _connect_factors(self, pre_id, post_id, rule, weight, what):
+        """snn_connect_factors of one (ConnectionRule, WeightRule or None) pair, and the arrays it points into (they must outlive the
+        call).  Without a factors rule the extension stays empty: the call then writes what snn_connect_by_spec writes."""
+        spec = self._connect_spec(pre_id, post_id, rule, weight, what)
+        if weight is None or weight.kind != WEIGHT_FACTORS:
+            return _lib.ConnectFactors(spec, 0, 0, 0.0, None, None), ()
+        shapes = self._lattice_shape(pre_id), self._lattice_shape(post_id)
+        if None in shapes:                               # an unknown id: sized for nothing, refused by the call before it reads them
+            u = v = np.zeros((weight.pre_factors if weight.pre_factors is not None else weight.post_factors).shape[0])
+        else:
+            u, v = (np.ascontiguousarray(f) for f in weight.factor_arrays(*shapes))       # ValueError: lengths that do not fit
+        item = _lib.ConnectFactors(spec, (u.shape[0]), int(weight.drop_zero), weight.scale, u.ctypes.data_as(_lib.f64p), v.ctypes.data_as(_lib.f64p))
+        return item, (u, v)
+
     def _connect_spec(self, pre_id, post_id, rule, weight, what):
         """snn_connect_spec of one (ConnectionRule, WeightRule or None) pair; the spec points into weight.table"""
         weight = WeightRule.constant(1.0) if weight is None else weight
@@ -502,6 +598,10 @@ class DeviceNetwork:
         """the reference's connect(...) between lattice `pre_id` and neuron lattice `post_id` (the same id: internally), evaluated
         on the device (snn_connect_by_spec): `rule` a ConnectionRule, `weight` a WeightRule (None: every edge weighs 1).
         rule.mask / weight.values are the same graph on the host (rule_pairs: a NaN of a displacement table is no edge)."""
+        if weight is not None and isinstance(weight, WeightRule) and weight.kind == WEIGHT_FACTORS:
+            item, keep = self._connect_factors(pre_id, post_id, rule, weight, "connect_by_rule")
+            self._check(self._L.snn_connect_by_factors(self._h, C.byref(item)))
+            return
         spec = self._connect_spec(pre_id, post_id, rule, weight, "connect_by_rule")
         self._check(self._L.snn_connect_by_spec(self._h, C.byref(spec)))
 
@@ -510,12 +610,21 @@ class DeviceNetwork:
         (pre_id, post_id, ConnectionRule, WeightRule or None), applied in order and committed once.  Every edge outside the plan's
         blocks keeps its current weight; traces, dw and counters of the whole graph restart at 0.  The committed edge order is
         graph_csr_structure()'s.  A displacement table visits the candidates of its rule: on a large handle give it a radius."""
-        specs = (_lib.ConnectSpec * max(len(plan), 1))()
         for k, entry in enumerate(plan):
             if not isinstance(entry, (tuple, list)) or len(entry) != 4:
                 raise TypeError(f"plan[{k}] must be (pre_id, post_id, ConnectionRule, WeightRule or None)")
-            specs[k] = self._connect_spec(*entry, f"plan[{k}]: connect_sparse")
-        self._check(self._L.snn_connect_by_specs_csr(self._h, specs, len(plan)))
+        if any(isinstance(entry[3], WeightRule) and entry[3].kind == WEIGHT_FACTORS for entry in plan):
+            # record kinds mix in one call: the factors form takes every spec, and reads its extension for factors records only
+            items, keep = (_lib.ConnectFactors * len(plan))(), []
+            for k, entry in enumerate(plan):
+                items[k], arrays = self._connect_factors(*entry, f"plan[{k}]: connect_sparse")
+                keep.append(arrays)
+            self._check(self._L.snn_connect_by_factors_csr(self._h, items, len(plan)))
+        else:
+            specs = (_lib.ConnectSpec * max(len(plan), 1))()
+            for k, entry in enumerate(plan):
+                specs[k] = self._connect_spec(*entry, f"plan[{k}]: connect_sparse")
+            self._check(self._L.snn_connect_by_specs_csr(self._h, specs, len(plan)))
         nnz = C.c_uint64()
         self._check(self._L.snn_graph_csr_nnz(self._h, C.byref(nnz)))
         self._nnz = int(nnz.value)
