@@ -750,6 +750,31 @@ int snn_get_peak_counts(snn_network_t *net, uint32_t id, uint64_t first_step, ui
 int snn_get_peaks(snn_network_t *net, uint32_t id, uint64_t first_step, uint64_t *ptr, uint32_t *steps, uint64_t capacity,
                   uint64_t *total);
 
+/* Voltage-peak totals: the NUMBERS the experiments take from that readout -- per window, firing_rates[i][n] = the peaks j with
+ * i - window < j <= i (hd_model.py), or the peaks at or after a first window (pipeline_setup.py) -- counted per neuron where the
+ * neuron is updated, as the spike totals of snn_set_reduced_history are: no raster, no launch of their own, and NO step form
+ * changes (the one-launch run, the fast sparse steps, the 24-bit image and deferred weight updates stay as they are).
+ * The series x[k] of a neuron is its voltage after the k-th step since the totals were last restarted, the binary32 a
+ * voltage-history row of that step holds.  It is EVERY step: it neither follows snn_set_history_stride nor shares the axis of
+ * snn_history_steps, and switching other records does not restart it.  It restarts (counts zero, k = 0) with a
+ * snn_set_peak_totals call that changes anything for any lattice and with snn_reset_history; a call that changes nothing
+ * restarts nothing.  A peak is the peak record's (above), threshold included; it is counted when its plateau ends, so a plateau
+ * still open at a getter call is not counted yet, and a plateau across a restart never is.  (A plateau of 2^31 samples or more
+ * is not followed.)  A peak at index p of lattice `id` goes to bucket b: p < origin is not counted; window == 0 is one
+ * open-ended bucket (n_windows must be 1); otherwise b = (p - origin) / window, and b >= n_windows is not counted.  origin = 1,
+ * window = W: row k - 1 is the experiments' firing_rates[k * W]; origin = first_window, window = 0: the pipelines' vector.
+ * snn_set_peak_totals: a NaN threshold, n_windows == 0 with enable, window == 0 with n_windows != 1, a spike-train lattice or an
+ * unknown id: SNN_ERR_BAD_ARG; a handle that is not finalized or is one of several shards: SNN_ERR_BAD_STATE (a single-shard
+ * handle is covered).  A call that fails while it allocates leaves the handle as it was.  Totals and the peak record are
+ * independent: both may be on, with different thresholds.
+ * snn_get_peak_totals: dst[n_windows][count]; n_windows must be the lattice's and count rows*cols (SNN_ERR_DIM_MISMATCH); a
+ * lattice whose totals are off: SNN_ERR_BAD_STATE.  snn_peak_totals_steps: samples seen since the restart.
+ * Memory: 12 B per neuron and 4 B per neuron and bucket of the lattice with the most buckets. */
+int snn_set_peak_totals(snn_network_t *net, uint32_t id, int enable, float threshold, uint64_t origin, uint32_t window,
+                        uint32_t n_windows);
+int snn_get_peak_totals(snn_network_t *net, uint32_t id, uint32_t *dst, size_t n_windows, size_t count);
+int snn_peak_totals_steps(const snn_network_t *net, uint64_t *steps);
+
 /* Strided capture: store the history rows (voltage, raster, reduced rows) of every `every`-th step only -- steps
  * 0, every, 2*every, ... counted from the last (re)start of the record; 1 = every step (the reference's
  * behaviour).  Changing the stride restarts the record.  Spike totals (below) always count every step. */

@@ -301,6 +301,9 @@ SIGNATURES = {
     "snn_get_peak_raster": (C.c_int, [H, C.c_uint32, u8p, C.c_size_t]),
     "snn_get_peak_counts": (C.c_int, [H, C.c_uint32, C.c_uint64, u32p, C.c_size_t]),
     "snn_get_peaks": (C.c_int, [H, C.c_uint32, C.c_uint64, u64p, u32p, C.c_uint64, u64p]),
+    "snn_set_peak_totals": (C.c_int, [H, C.c_uint32, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "snn_get_peak_totals": (C.c_int, [H, C.c_uint32, u32p, C.c_size_t, C.c_size_t]),
+    "snn_peak_totals_steps": (C.c_int, [H, u64p]),
     "snn_set_history_stride": (C.c_int, [H, C.c_uint32]),
     "snn_set_reduced_history": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]),
     "snn_get_average_voltage_history": (C.c_int, [H, C.c_uint32, f32p, C.c_size_t]),

@@ -2,19 +2,15 @@
 // step one bit, set where scipy.signal.find_peaks(x) reports a local maximum of the neuron's recorded voltage series x and
 // x[index] > threshold -- the readout of the reference's GPU experiments (find_peaks_above_threshold over the [T, N] voltage
 // history), without the history.  Streaming form, per neuron `prev` (the previous recorded sample) and `left` (the sample index at
-// which the series last rose, PEAK_NONE when it has fallen since); at recorded sample t >= 1 with value v:
-//     v > prev : left = t
-//     v == prev: nothing (a plateau goes on)
-//     else     : if (left != NONE && v < prev && prev > threshold) peak at (left + t - 1) / 2;  left = NONE     (NaN lands here)
-// then prev = v; sample 0 sets prev = v, left = NONE.  A peak is known only when its plateau has ended: its bit goes into a PAST
-// row of the raster.  The raster has the spike raster's layout, [rows][n_pad / 64] words of 64 bits, neuron q at bit q % 64 of
-// word q / 64.
+// which the series last rose, PEAK_NONE when it has fallen since): the rule of snn_kernels_peak_totals.hpp (peak_rule), which the
+// peak totals share, with mark(t) = t; a plateau that ends at recorded sample t is a peak at (left + t - 1) / 2; sample 0 sets
+// prev = v, left = NONE.  A peak is known only when its plateau has ended: its bit goes into a PAST row of the raster.  The raster
+// has the spike raster's layout, [rows][n_pad / 64] words of 64 bits, neuron q at bit q % 64 of word q / 64.
 #pragma once
+#include "snn_kernels_peak_totals.hpp"
 #include "snn_layout.hpp"
 
 namespace snn {
-
-constexpr uint32_t PEAK_NONE = 0xFFFFFFFFu;
 
 struct PeakArgs {
     const float *xbuf;                // the voltage plane this step's history row was written from
@@ -46,17 +42,12 @@ __global__ __launch_bounds__(256) void k_peak_detect(const PeakArgs a)
             if (a.t == 0) {
                 a.left[q] = PEAK_NONE;
             } else {
-                const float p = a.prev[q];
-                if (v > p) {
-                    a.left[q] = a.t;
-                } else if (!(v == p)) {
-                    const uint32_t l = a.left[q];
-                    if (l != PEAK_NONE) {
-                        hit = v < p && p > __uint_as_float(c.y);
-                        row = (l + a.t - 1u) >> 1;              // l >= 1, t <= 2^32 - 2: no wrap below 2^32 rows (grow_history)
-                        a.left[q] = PEAK_NONE;
-                    }
-                }
+                const uint32_t l0 = a.left[q];
+                uint32_t l = l0;
+                const PeakClosed e = peak_rule(v, a.prev[q], l, a.t, __uint_as_float(c.y));
+                hit = e.hit;
+                if (e.ended) row = (e.left + a.t - 1u) >> 1;    // left >= 1, t <= 2^32 - 2: no wrap below 2^32 rows (grow_history)
+                if (l != l0) a.left[q] = l;
             }
             a.prev[q] = v;
         }

@@ -666,6 +666,10 @@ __device__ __forceinline__ void run_resident_steps(const ResidentRunArgs &a, Res
     float nv = 0.0f, n2 = 0.0f, n_div = 1.0f;        // voltage; Izhikevich w / refractory_count; the averager's divisor
     float pr[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // the model's parameters (see below)
     uint32_t n_spikes = 0, last_spike = 0;
+    // voltage-peak totals (snn_kernels_peak_totals.hpp): the neuron's streaming state, written back with the rest below; a peak
+    // goes to its bucket in memory when its plateau ends (a run that gives up is rolled back from the snapshot, counts included)
+    float pt_prev = 0.0f, pt_threshold = 0.0f;
+    uint32_t pt_left = PEAK_NONE;
     // ... and, CHEM (Izhikevich only): per type the receptor (r, current, g, e, kinetics parameters, input count) and the
     // transmitter (t, its kinetics parameters); c_flags bit k: receptor present, bit 8 + k: the neuron releases the type
     // (the constants of the kinetics wait in LDS: ResidentRunShared::chem_par)
@@ -697,6 +701,12 @@ __device__ __forceinline__ void run_resident_steps(const ResidentRunArgs &a, Res
             pr[0] = n.slif_g[q]; pr[1] = n.slif_e[q]; pr[2] = dt; pr[5] = n.v_reset[q]; pr[6] = n.v_th[q];
         }
         last_spike = reinterpret_cast<const uint32_t *>(n.xbuf)[n.xl.at(q, PLANE_SPIKE)];
+        if (!CHEM && a.up.pt.block) {
+            const uint32_t *s = a.up.pt.block + q;
+            pt_prev = __uint_as_float(s[(size_t)PT_PREV * n.n_pad]);
+            pt_left = s[(size_t)PT_LEFT * n.n_pad];
+            pt_threshold = __uint_as_float(s[(size_t)PT_THRESHOLD * n.n_pad]);
+        }
         if (CHEM) {
             // Izhikevich with chemical synapses, built-in kinetics: receptors and transmitters in registers too (ChemStep's
             // arithmetic, snn_kernels_update.hpp; iterate_and_spike/mod.rs:1186-1304, 148-196)
@@ -1422,6 +1432,11 @@ __device__ __forceinline__ void run_resident_steps(const ResidentRunArgs &a, Res
                         n_spikes += 1;
                     }
                     if (vhist_row) vhist_row[q] = v_new;
+                    if (b.up.pt.block) {
+                        // (the chemical form has no registers to spare: its state stays in memory)
+                        if (CHEM) peak_totals_sample(b.up.pt, b.up.n.n_pad, q, v_new, b.up.pt.t0 + s);
+                        else peak_totals_step(b.up.pt, b.up.n.n_pad, q, v_new, b.up.pt.t0 + s, pt_prev, pt_left, pt_threshold);
+                    }
                 }
             } else {
                 const ResidentRunArgs &b = a;
@@ -1526,6 +1541,10 @@ __device__ __forceinline__ void run_resident_steps(const ResidentRunArgs &a, Res
                 }
             }
             if (a.up.spike_counts && n_spikes) a.up.spike_counts[q] += n_spikes;
+            if (!CHEM && a.up.pt.block) {
+                a.up.pt.block[(size_t)PT_PREV * n.n_pad + q] = __float_as_uint(pt_prev);
+                a.up.pt.block[(size_t)PT_LEFT * n.n_pad + q] = pt_left;
+            }
         }
         if (a.timing && lane == 0)
             for (int k = 0; k < 4; ++k) a.timing[blockIdx.x * 4 + k] = spent[k];

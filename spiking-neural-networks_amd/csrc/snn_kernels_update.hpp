@@ -12,6 +12,7 @@
 // operation order (no FMA contraction in this TU).
 #pragma once
 #include "snn_custom_model.hpp"
+#include "snn_kernels_peak_totals.hpp"
 #include "snn_layout.hpp"
 #include "snn_math.hpp"
 
@@ -30,6 +31,7 @@ struct UpdateArgs {
     float *vhist_row;          // this step's row of the voltage history (global neuron index) or null
     unsigned long long *spike_row;   // this step's row of the bit-packed raster or null
     uint32_t *spike_counts;          // per-neuron spike totals (SpikeHistory::aggregate) or null
+    PeakTotalsArgs pt;               // voltage-peak totals (pt.block null: off); pt.t0 = the sample index of the step at `clock`
     // Where the exchanged state (V, spike flag, t) of the step is stored: `xout` = the handle's exchange buffer
     // (= n.xbuf on the two-kernel path, which updates in place); the fused small-lattice step reads S(t) from a
     // shadow copy (n.xbuf) while it writes S(t+1) to the exchange buffer and to the other shadow (`xout2`).
@@ -629,6 +631,7 @@ __device__ __forceinline__ uint32_t update_neuron_at(const UpdateArgs &a, uint32
         if (spike) a.n.last_firing_time[q] = (int32_t)clock;     // neuron/mod.rs:964-966, 2555-2557
         if (vhist_row) vhist_row[q] = v_new;
         if (a.spike_counts && spike) a.spike_counts[q] += 1;
+        if (a.pt.block) peak_totals_sample(a.pt, a.n.n_pad, q, v_new, a.pt.t0 + (unsigned long long)(clock - a.clock));
         if (v_stored) *v_stored = v_new;
     }
     return spike;

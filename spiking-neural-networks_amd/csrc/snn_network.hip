@@ -865,6 +865,11 @@ int snn_reset_history(snn_network_t *net) ABI_TRY
         TRY(end_run(net));
         HIP_TRY(memset_sync(net, net->spike_counts, 0, (size_t)net->n_pad * 4), SNN_ERR_BUFFER_WRITE);
     }
+    if (net->finalized && net->pt_block) {       // the voltage-peak totals start over with the spike totals
+        HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
+        TRY(end_run(net));
+        TRY(peak_totals_restart(net));
+    }
     return SNN_OK;
 }
 ABI_CATCH
@@ -964,6 +969,21 @@ ABI_CATCH
 int snn_get_peaks(snn_network_t *net, uint32_t id, uint64_t first_step, uint64_t *ptr, uint32_t *steps, uint64_t capacity,
                   uint64_t *total) ABI_TRY
 { return get_peaks(net, id, first_step, ptr, steps, capacity, total); }
+ABI_CATCH
+
+int snn_set_peak_totals(snn_network_t *net, uint32_t id, int enable, float threshold, uint64_t origin, uint32_t window,
+                        uint32_t n_windows) ABI_TRY
+{ return set_peak_totals(net, id, enable, threshold, origin, window, n_windows); }
+ABI_CATCH
+int snn_get_peak_totals(snn_network_t *net, uint32_t id, uint32_t *dst, size_t n_windows, size_t count) ABI_TRY
+{ return get_peak_totals(net, id, dst, n_windows, count); }
+ABI_CATCH
+int snn_peak_totals_steps(const snn_network_t *net, uint64_t *steps) ABI_TRY
+{
+    if (!net || !steps) return fail(SNN_ERR_BAD_ARG, "null argument");
+    *steps = net->cur.pt_steps;
+    return SNN_OK;
+}
 ABI_CATCH
 
 int snn_set_history_stride(snn_network_t *net, uint32_t every) ABI_TRY

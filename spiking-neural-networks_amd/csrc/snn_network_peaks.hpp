@@ -160,4 +160,106 @@ int get_peaks(snn_network *net, uint32_t id, uint64_t first_step, uint64_t *ptr,
     return SNN_OK;
 }
 
+// ---- voltage-peak totals (snn_set_peak_totals / snn_get_peak_totals / snn_peak_totals_steps; snn_kernels_peak_totals.hpp) ----
+
+// The series starts over: no sample seen, nothing to rise from (prev = NaN, left = NONE: both all-ones words), counts zero.
+int peak_totals_restart(snn_network *net)
+{
+    if (!net->pt_block) return SNN_OK;
+    if (hipMemsetAsync(net->pt_block, 0xFF, (size_t)2 * net->n_pad * 4, net->stream) != hipSuccess ||
+        hipMemsetAsync(net->pt_counts, 0, (size_t)net->pt_rows * net->n_pad * 4, net->stream) != hipSuccess ||
+        hipStreamSynchronize(net->stream) != hipSuccess)
+        return fail(SNN_ERR_BUFFER_WRITE, "the fill of the peak totals' state failed");
+    net->cur.pt_steps = 0;
+    return SNN_OK;
+}
+
+int set_peak_totals(snn_network *net, uint32_t id, int enable, float threshold, uint64_t origin, uint32_t window, uint32_t n_windows)
+{
+    static_assert(PT_PREV == 0 && PT_LEFT == 1, "peak_totals_restart fills the first two rows of the block");
+    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
+    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized: peak totals are switched on a finalized handle");
+    const LatticeInfo *l = find_lattice(net, id);
+    if (!l || l->spike_train) return fail(SNN_ERR_BAD_ARG, "peak totals belong to neuron lattices");
+    if (threshold != threshold) return fail(SNN_ERR_BAD_ARG, "the threshold is NaN: no voltage is above it");
+    if (enable && n_windows == 0) return fail(SNN_ERR_BAD_ARG, "n_windows is 0: nothing to count into");
+    if (enable && window == 0 && n_windows != 1) return fail(SNN_ERR_BAD_ARG, "window 0 is one open-ended bucket: n_windows must be 1");
+    if (net->sharded && net->n_shards > 1)
+        return fail(SNN_ERR_BAD_STATE, "peak totals need an unsharded handle or a single shard: one of several shards is not covered");
+    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
+    TRY(end_run(net));
+    using Setting = snn_network::PeakTotalsSetting;
+    const size_t nl = std::max<size_t>(1, net->lattices.size()), np = net->n_pad;
+    Setting want;
+    if (enable) { want.on = true; want.threshold = threshold; want.origin = origin; want.window = window; want.n_windows = n_windows; }
+    if (net->pt_cfg_host.empty() && !enable) return SNN_OK;
+    if (net->pt_cfg_host.size() == nl) {
+        const Setting &have = net->pt_cfg_host[l->slot];
+        if (have.on == want.on && __builtin_bit_cast(uint32_t, have.threshold) == __builtin_bit_cast(uint32_t, want.threshold) &&
+            have.origin == want.origin && have.window == want.window && have.n_windows == want.n_windows)
+            return SNN_OK;
+    }
+    // ---- everything that can fail, into locals: a refused call leaves the handle as it was ----
+    hvec<Setting> cfg(net->pt_cfg_host);
+    if (cfg.empty()) cfg.assign(nl, Setting{});
+    cfg[l->slot] = want;
+    // the block as a restarted series finds it: state rows all ones, every neuron the setting of its lattice (off: a NaN threshold)
+    hvec<uint32_t> block((size_t)PT_ROWS * np, 0u);
+    std::fill(block.begin(), block.begin() + (size_t)(PT_THRESHOLD + 1) * np, 0xFFFFFFFFu);
+    uint32_t rows = 1;
+    bool any = false;
+    for (const auto &lat : net->lattices) {
+        const Setting &c = cfg[lat.slot];
+        if (lat.spike_train || !c.on) continue;
+        any = true;
+        rows = std::max(rows, c.n_windows);
+        const uint32_t word[PT_ROWS] = {0xFFFFFFFFu, 0xFFFFFFFFu, __builtin_bit_cast(uint32_t, c.threshold), (uint32_t)c.origin,
+                                        (uint32_t)(c.origin >> 32), c.window, c.n_windows};
+        for (int r = PT_THRESHOLD; r < PT_ROWS; ++r)
+            std::fill(block.begin() + (size_t)r * np + lat.first, block.begin() + (size_t)r * np + lat.first + lat.count, word[r]);
+    }
+    TRY(ensure_copy_stage(net));
+    // registered arrays, fresh ones: snapshots, "verify" and snn_debug_checkpoint carry the state and the counts, row by row
+    uint32_t *block_d = nullptr, *counts_d = nullptr;
+    int rc = dev_alloc(net, reinterpret_cast<void **>(&block_d), (size_t)PT_ROWS * np * 4, /*scratch=*/false, /*slice=*/np * 4);
+    if (rc == SNN_OK) rc = dev_alloc(net, reinterpret_cast<void **>(&counts_d), (size_t)rows * np * 4, /*scratch=*/false, /*slice=*/np * 4);
+    if (rc == SNN_OK && copy_sync(net, block_d, block.data(), block.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+        rc = fail(SNN_ERR_BUFFER_WRITE, "the upload of the peak totals' settings failed");
+    if (rc == SNN_OK && (hipMemsetAsync(counts_d, 0, (size_t)rows * np * 4, net->stream) != hipSuccess || hipStreamSynchronize(net->stream) != hipSuccess))
+        rc = fail(SNN_ERR_BUFFER_WRITE, "the fill of the peak totals' counts failed");
+    if (rc != SNN_OK) {
+        dev_replace(net, block_d);
+        dev_replace(net, counts_d);
+        return rc;
+    }
+    // ---- the commit (nothing below fails): the series of every lattice starts over ----
+    dev_replace(net, net->pt_block);
+    dev_replace(net, net->pt_counts);
+    net->pt_cfg_host.swap(cfg);
+    net->pt_block = block_d; net->pt_counts = counts_d; net->pt_rows = rows;
+    net->want_pt = any;
+    net->pk_epoch += 1;                    // (a checkpoint taken before this call no longer fits the handle)
+    net->cur.pt_steps = 0;
+    return SNN_OK;
+}
+
+int get_peak_totals(snn_network *net, uint32_t id, uint32_t *dst, size_t n_windows, size_t count)
+{
+    if (!net) return fail(SNN_ERR_BAD_ARG, "net is null");
+    if (!net->finalized) return fail(SNN_ERR_BAD_STATE, "network not finalized");
+    const LatticeInfo *l = find_lattice(net, id);
+    if (!l || l->spike_train) return fail(SNN_ERR_BAD_ARG, "peak totals belong to neuron lattices");
+    if (net->pt_cfg_host.empty() || !net->pt_cfg_host[l->slot].on)
+        return fail(SNN_ERR_BAD_STATE, "the peak totals of this lattice are off (snn_set_peak_totals)");
+    if (n_windows != net->pt_cfg_host[l->slot].n_windows) return fail(SNN_ERR_DIM_MISMATCH, "n_windows must equal the lattice's setting");
+    if (count != l->count) return fail(SNN_ERR_DIM_MISMATCH, "count must equal rows*cols");
+    if (count == 0) return SNN_OK;
+    if (!dst) return fail(SNN_ERR_BAD_ARG, "dst is null");
+    HIP_TRY(hipSetDevice(net->device), SNN_ERR_GET_DEVICE);
+    TRY(end_run(net));
+    HIP_TRY(copy2d_sync(net, dst, count * 4, net->pt_counts + l->first, (size_t)net->n_pad * 4, count * 4, n_windows, hipMemcpyDeviceToHost),
+            SNN_ERR_BUFFER_READ);
+    return SNN_OK;
+}
+
 } // namespace

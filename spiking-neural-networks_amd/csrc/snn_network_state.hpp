@@ -194,6 +194,7 @@ struct LatticeInfo {
 struct Cursors {
     long long clock = 0, run_step_offset = 0;        // (the steps of the open run the spike-train lattices' host clocks do not hold yet)
     uint64_t hist_steps = 0, hist_tick = 0;          // history rows stored, steps seen since the record was (re)started
+    uint64_t pt_steps = 0;                           // samples the voltage-peak totals have seen since their last restart
 };
 // Which caches of the handle are current; a checkpoint carries it whole.
 struct CacheState {
@@ -356,7 +357,8 @@ struct snn_network {
     hipEvent_t ev_packed = nullptr, ev_exchanged = nullptr;
 
     // the registry (dev_alloc, ascending address); the generation counts additions and removals
-    struct Registered { dev_ptr<void> mem; size_t bytes; bool scratch; };
+    // slice != 0: an array of rows of `slice` bytes that run_snapshot takes row by row, whatever its size
+    struct Registered { dev_ptr<void> mem; size_t bytes; bool scratch; size_t slice = 0; };
     hvec<Registered> registry;
     uint64_t registry_generation = 0;
     // sparse form (CSR by local postsynaptic row); the arrays are replaced by every snn_set_graph_csr
@@ -501,6 +503,14 @@ struct snn_network {
     uint32_t *pk_left = nullptr;
     dev_ptr<unsigned long long> pk_raster;
     uint64_t pk_epoch = 0;
+    // voltage-peak totals (snn_set_peak_totals, snn_kernels_peak_totals.hpp): per neuron lattice slot the setting on the host; on the
+    // device the per-neuron block [PT_ROWS][n_pad] (streaming state, then each neuron's setting) and the counts [pt_rows][n_pad] --
+    // registered arrays in slices of one row, so that every snapshot takes them whatever their size
+    struct PeakTotalsSetting { bool on = false; float threshold = 0.0f; uint64_t origin = 0; uint32_t window = 0, n_windows = 0; };
+    hvec<PeakTotalsSetting> pt_cfg_host;
+    bool want_pt = false;
+    uint32_t *pt_block = nullptr, *pt_counts = nullptr;
+    uint32_t pt_rows = 0;
     float eeg_ref = 0.007f, eeg_dist = 0.8f, eeg_cond = 251.0f;     // EEGHistory defaults, neuron/mod.rs:246-255
     dev_ptr<float> summ_avg, summ_eeg;                              // [cap][n_lattices]
     uint32_t *spike_counts = nullptr, *lat_first_dev = nullptr, *lat_count_dev = nullptr;
@@ -710,14 +720,14 @@ auto registry_slot(snn_network *net, const void *p)
     auto below = [](const snn_network::Registered &r, const void *q) { return std::less<const void *>()(r.mem.get(), q); };
     return std::lower_bound(net->registry.begin(), net->registry.end(), p, below);
 }
-int dev_alloc(snn_network *net, void **out, size_t bytes, bool scratch = false)
+int dev_alloc(snn_network *net, void **out, size_t bytes, bool scratch = false, size_t slice = 0)
 {
     *out = nullptr;
     if (bytes == 0) bytes = 256;
     dev_ptr<void> mem;
     HIP_TRY(alloc_streamed(&mem, bytes), SNN_ERR_BUFFER_CREATE);
     void *const p = mem;
-    net->registry.insert(registry_slot(net, p), snn_network::Registered{std::move(mem), bytes, scratch});
+    net->registry.insert(registry_slot(net, p), snn_network::Registered{std::move(mem), bytes, scratch, slice});
     net->registry_generation += 1;
     *out = p;
     HIP_TRY(poison_if_asked(p, bytes), SNN_ERR_BUFFER_WRITE);
@@ -739,7 +749,7 @@ dev_ptr<void> dev_replace(snn_network *net, const void *old, dev_ptr<void> fresh
     net->registry.erase(it);
     if (fresh) {
         void *const p = fresh;
-        net->registry.insert(registry_slot(net, p), snn_network::Registered{std::move(fresh), r.bytes, r.scratch});
+        net->registry.insert(registry_slot(net, p), snn_network::Registered{std::move(fresh), r.bytes, r.scratch, r.slice});
     }
     net->registry_generation += 1;
     return std::move(r.mem);

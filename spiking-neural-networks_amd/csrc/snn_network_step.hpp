@@ -251,6 +251,15 @@ int launch_inputs(snn_network *net, InputsPart part = INPUTS_ALL)
     return profile_close(net, e1);
 }
 
+// the voltage-peak totals' part of a launch's UpdateArgs (null: off)
+PeakTotalsArgs peak_totals_args(const snn_network *net)
+{
+    PeakTotalsArgs pt{};
+    if (!net->want_pt) return pt;
+    pt.block = net->pt_block; pt.counts = net->pt_counts; pt.t0 = net->cur.pt_steps;
+    return pt;
+}
+
 int launch_update(snn_network *net)
 {
     if (net->n_loc == 0) return SNN_OK;
@@ -263,6 +272,7 @@ int launch_update(snn_network *net)
     a.vhist_row = (record_now(net) && net->want_vhist && net->vhist) ? net->vhist + (size_t)net->cur.hist_steps * net->n_pad : nullptr;
     a.spike_row = (record_now(net) && net->want_raster && net->raster) ? net->raster + (size_t)net->cur.hist_steps * (net->n_pad / 64) : nullptr;
     a.spike_counts = net->want_counts ? net->spike_counts : nullptr;
+    a.pt = peak_totals_args(net);
     a.xout = net->xbuf; a.xout2 = nullptr;
     a.has_nt = net->any_nt_neurons ? 1 : 0;
     a.live_mask = net->cache.live_mask_applied;       // transmitter types some neuron or cell releases (ensure_counts; all ones: unknown)
@@ -811,6 +821,7 @@ int fused_step_args(snn_network *net, InputsArgs &a, UpdateArgs &u, bool in_plac
     u.vhist_row = (record_now(net) && net->want_vhist && net->vhist) ? net->vhist + (size_t)net->cur.hist_steps * net->n_pad : nullptr;
     u.spike_row = (record_now(net) && net->want_raster && net->raster) ? net->raster + (size_t)net->cur.hist_steps * (net->n_pad / 64) : nullptr;
     u.spike_counts = net->want_counts ? net->spike_counts : nullptr;
+    u.pt = peak_totals_args(net);
     u.xout = net->xbuf; u.xout2 = next;
     u.has_nt = net->any_nt_neurons ? 1 : 0;
     u.live_mask = net->cache.live_mask_applied;
@@ -942,7 +953,17 @@ int run_snapshot(snn_network *net, bool restore)
         size_t words = 0;
         uint32_t max_words = 0;
         for (const auto &r : net->registry) {
-            if (r.scratch || r.bytes > limit) continue;
+            if (r.scratch) continue;
+            if (r.slice) {
+                // (an array the run writes that may exceed the limit -- the peak totals' counts: one entry per row)
+                for (size_t at = 0; at + r.slice <= r.bytes; at += r.slice) {
+                    table.push_back(CopyEntry{reinterpret_cast<uint32_t *>(static_cast<char *>(r.mem.get()) + at), nullptr, (uint32_t)(r.slice / 4), 0u});
+                    words += r.slice / 4;
+                    max_words = std::max(max_words, (uint32_t)(r.slice / 4));
+                }
+                continue;
+            }
+            if (r.bytes > limit) continue;
             const uint32_t w = (uint32_t)(r.bytes / 4);
             // pad = 1: contents depend on the order of atomics (the compacted spike list) -- copied, but not compared by "verify"
             table.push_back(CopyEntry{static_cast<uint32_t *>(r.mem.get()), nullptr, w, r.mem.get() == (void *)net->spike_list ? 1u : 0u});
@@ -1116,6 +1137,7 @@ int launch_run_resident(snn_network *net, uint64_t iterations, uint64_t steps_be
         net->stat.run.steps += steps;
         net->cur.clock += steps;
         net->cur.run_step_offset += steps;
+        if (net->want_pt) net->cur.pt_steps += steps;
         if (recording(net)) { net->cur.hist_steps += steps; net->cur.hist_tick += steps; }
     }
     return SNN_OK;
@@ -1351,6 +1373,7 @@ int step_end(snn_network *net)
         net->cells_stepped = false;
         net->cur.clock += 1;
         net->cur.run_step_offset += 1;
+        if (net->want_pt) net->cur.pt_steps += 1;
         if (record_now(net)) net->cur.hist_steps += 1;
         if (recording(net)) net->cur.hist_tick += 1;
         return SNN_OK;
@@ -1409,6 +1432,7 @@ int step_end(snn_network *net)
     if (!net->cells_stepped) TRY(launch_spike_trains(net, 1, net->cur.run_step_offset, net->cur.clock));
     net->cells_stepped = false;
     net->cur.run_step_offset += 1;
+    if (net->want_pt) net->cur.pt_steps += 1;
     if (record_now(net)) net->cur.hist_steps += 1;
     if (recording(net)) net->cur.hist_tick += 1;
     return SNN_OK;

@@ -46,6 +46,10 @@ std::string describe_array(const snn_network *net, const void *ptr, uint32_t wor
         if (inside(net->shadow[i], plane * NUM_PLANES)) return "shadow " + std::to_string(i) + ", plane " + std::to_string(word / net->xl.stride) + ", neuron " + std::to_string(word % net->xl.stride);
     for (int i = 0; i < 2; ++i)
         if (inside(net->cell_view[i], (size_t)net->c_pad * 8)) return "cell view " + std::to_string(i) + ", word " + std::to_string(word);
+    if (inside(net->pt_counts, (size_t)net->pt_rows * net->n_pad * 4))       // (one snapshot entry per row)
+        return "peak totals: counts, bucket " + std::to_string((size_t)(p - (const char *)net->pt_counts) / 4 / net->n_pad) + ", neuron " + std::to_string(word);
+    if (inside(net->pt_block, (size_t)PT_ROWS * net->n_pad * 4))             // (row 0: previous sample, row 1: left edge, then settings)
+        return "peak totals: block, row " + std::to_string((size_t)(p - (const char *)net->pt_block) / 4 / net->n_pad) + ", neuron " + std::to_string(word);
     const struct { const void *base; const char *name; } known[] = {
         {net->part_i, "part_i"}, {net->part_t, "part_t"}, {net->n_in, "n_in"}, {net->tcount, "tcount"}, {net->W, "W"}, {net->w24, "24-bit image of W"},
         {net->spike_counts, "spike_counts"}, {net->spike_count, "spike_count"}, {net->st_clock_dev, "st_clock_dev"},

@@ -1408,6 +1408,8 @@ class LatticeNetworkGPU:
         self._plastic = set()           # ids of the lattices that ran with do_plasticity since the upload
         self._peak_settings = {}        # set_peak_history: lattice id -> threshold; kept across uploads of a fresh handle
         self._peak_applied = {}         # ... and what the current handle has been told
+        self._peak_totals_settings = {}  # set_peak_totals: lattice id -> (threshold, origin, window, n_windows), kept likewise
+        self._peak_totals_applied = {}
         # when a lattice's weight snapshot is taken: 2 = before the step's weight updates (LatticeNetwork::iterate,
         # neuron/mod.rs:2450-2461), 1 = after them (a lone Lattice, neuron/mod.rs:904-910 -- what LatticeGPU passes)
         self._graph_hist_order = graph_history_order
@@ -1504,6 +1506,7 @@ class LatticeNetworkGPU:
             self._edge_hist = None
             self._plastic = set()
             self._peak_applied = {}
+            self._peak_totals_applied = {}
 
     def _may_differ(self, lattice):
         """whether the handle's weights of a rule-held lattice may differ from what its rule gives: plasticity (STDP, BCM) was on
@@ -1693,6 +1696,7 @@ class LatticeNetworkGPU:
                 self._graph_hist[id] = l.update_graph_history
         self._edge_history_flags()
         self._peak_flags()
+        self._peak_totals_flags()
 
     def _block_edges(self, key, edges):
         """(pre, post) global indices of the edges of block (pre_id, post_id) as the handle holds them: a sparse handle filters its
@@ -1922,6 +1926,48 @@ class LatticeNetworkGPU:
             return np.zeros((l.rows, l.cols), np.uint32)
         return self._dn.peak_counts(id, window).reshape(l.rows, l.cols)
 
+    # ... and the numbers the experiments take from it, counted where the neurons are updated (DeviceNetwork.set_peak_totals): per
+    # window, hd_model.py's firing_rates[i][n] = len([j for j in peaks[n] if j <= i and j > i - window]) is row i // window - 1
+    # of origin=1, window=window; the pipelines' len([j for j in peaks if j >= first_window]) is origin=first_window, window=0.
+    def set_peak_totals(self, id, threshold=20.0, origin=0, window=0, n_windows=1, enable=True):
+        """Voltage-peak totals of lattice `id` over every step from now on; no step form changes.  The setting outlives the
+        device copy (a fresh handle counts from its own first step)."""
+        if id not in self.network.lattices:
+            raise KeyError(f"no neuron lattice {id}")
+        threshold = float(np.float32(threshold))
+        if threshold != threshold:
+            raise ValueError("the threshold is NaN")
+        origin, window, n_windows = int(origin), int(window), int(n_windows)
+        if enable and (n_windows < 1 or (window == 0 and n_windows != 1) or origin < 0 or window < 0):
+            raise ValueError("n_windows >= 1, and exactly 1 with window 0")
+        if enable:
+            self._peak_totals_settings[id] = (threshold, origin, window, n_windows)
+        else:
+            self._peak_totals_settings.pop(id, None)
+        if self._dn is not None:
+            self._peak_totals_flags()
+
+    def _peak_totals_flags(self):
+        dn = self._dn
+        for id in sorted(set(self._peak_totals_settings) | set(self._peak_totals_applied)):
+            want = self._peak_totals_settings.get(id) if id in self.network.lattices else None
+            if want != self._peak_totals_applied.get(id):
+                if want is None:
+                    dn.set_peak_totals(id, 0.0, enable=False)
+                    self._peak_totals_applied.pop(id, None)
+                else:
+                    dn.set_peak_totals(id, *want)
+                    self._peak_totals_applied[id] = want
+
+    def peak_totals(self, id):
+        """[n_windows][rows][cols] peaks per neuron and window; a peak is counted once its plateau has ended"""
+        l = self.network.lattices[id]
+        if id not in self._peak_totals_settings:
+            raise ValueError(f"the peak totals of lattice {id} are off")
+        if self._dn is None:
+            return np.zeros((self._peak_totals_settings[id][3], l.rows, l.cols), np.uint32)
+        return self._dn.peak_totals(id).reshape(-1, l.rows, l.cols)
+
     def close(self):
         self._dirty()
 
@@ -1936,6 +1982,7 @@ class LatticeGPU:
         self._sparse = bool(sparse)                                 # the handle holds a sparse (CSR) graph
         self._net = None
         self._peak_setting = None                                   # set_peak_history: the threshold, None while off
+        self._peak_totals_setting = None                            # set_peak_totals: (threshold, origin, window, n_windows)
 
     @classmethod
     def from_lattice(cls, lattice, device=0, sparse=False):     # gpu_lattices/mod.rs:496-511
@@ -1949,6 +1996,8 @@ class LatticeGPU:
             self._net = LatticeNetworkGPU(host, device=self._device, graph_history_order=1, sparse=self._sparse)
             if self._peak_setting is not None:
                 self._net.set_peak_history(self._lattice.id, self._peak_setting)
+            if self._peak_totals_setting is not None:
+                self._net.set_peak_totals(self._lattice.id, *self._peak_totals_setting)
         return self._net
 
     def _dirty(self):
@@ -2041,6 +2090,26 @@ class LatticeGPU:
         if self._net is None:
             return np.zeros((self._lattice.rows, self._lattice.cols), np.uint32)
         return self._net.peak_counts(self._lattice.id, window)
+
+    def set_peak_totals(self, threshold=20.0, origin=0, window=0, n_windows=1, enable=True):
+        """the voltage-peak totals of the lattice (LatticeNetworkGPU.set_peak_totals); kept across rebuilds of the device copy"""
+        threshold = float(np.float32(threshold))
+        if threshold != threshold:
+            raise ValueError("the threshold is NaN")
+        setting = (threshold, int(origin), int(window), int(n_windows))
+        if enable and (setting[3] < 1 or (setting[2] == 0 and setting[3] != 1) or setting[1] < 0 or setting[2] < 0):
+            raise ValueError("n_windows >= 1, and exactly 1 with window 0")
+        self._peak_totals_setting = setting if enable else None
+        if self._net is not None:
+            self._net.set_peak_totals(self._lattice.id, *setting, enable=enable)
+
+    def peak_totals(self):
+        """[n_windows][rows][cols]"""
+        if self._peak_totals_setting is None:
+            raise ValueError("the peak totals are off")
+        if self._net is None:
+            return np.zeros((self._peak_totals_setting[3], self._lattice.rows, self._lattice.cols), np.uint32)
+        return self._net.peak_totals(self._lattice.id)
 
     def reset_timing(self):
         if self._net is not None:

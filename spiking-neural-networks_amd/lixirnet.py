@@ -15,7 +15,8 @@ against it unchanged apart from the import (`from snn_amd import lixirnet as ln`
 classes only build; stepping lives on the `*GPU` classes (there is no CPU stepper in this package).
 
 Beyond the reference's methods the two `*GPU` classes carry the device-side readout of its experiments
-(`set_peak_history`, `peaks`, `peak_counts`: find_peaks_above_threshold without the voltage history).
+(`set_peak_history`, `peaks`, `peak_counts`: find_peaks_above_threshold without the voltage history) and its counts per
+window (`set_peak_totals`, `peak_totals`: the experiments' firing_rates, kept in every step form).
 
 The library is compiled the first time one of the names is touched (hipcc, about a minute, once per checkout).
 """

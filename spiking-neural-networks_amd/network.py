@@ -355,6 +355,7 @@ class DeviceNetwork:
                                               C.byref(self._h)))
         self.model = model
         self.lattices = {}          # id -> (rows, cols, is_spike_train)
+        self._peak_totals_rows = {}  # id -> n_windows of set_peak_totals
         self.finalized = False
 
     def _check(self, code):
@@ -1028,6 +1029,31 @@ class DeviceNetwork:
             steps = np.zeros(int(total.value), np.uint32)
         flat = steps.astype(np.int64)
         return [flat[int(ptr[i]):int(ptr[i + 1])] for i in range(rows * cols)]
+
+    def set_peak_totals(self, id, threshold, origin=0, window=0, n_windows=1, enable=True):
+        """Voltage-peak totals of neuron lattice `id` (snn_set_peak_totals): per neuron the NUMBER of peaks above `threshold`
+        of its voltage series over every step since the call, in buckets b = (index - origin) // window (window 0: one
+        open-ended bucket from `origin` on).  No step form changes; a call that changes something restarts the totals of
+        every lattice, and so does reset_history."""
+        self._check(self._L.snn_set_peak_totals(self._h, id, int(bool(enable)), float(threshold), int(origin), int(window),
+                                                int(n_windows)))
+        if enable:
+            self._peak_totals_rows[id] = int(n_windows)
+        else:
+            self._peak_totals_rows.pop(id, None)
+
+    def peak_totals(self, id):
+        """uint32[n_windows, rows*cols]; a peak is counted once its plateau has ended"""
+        rows, cols, _ = self.lattices[id]
+        out = _out((self._peak_totals_rows.get(id, 1), rows * cols), np.uint32)
+        self._check(self._L.snn_get_peak_totals(self._h, id, out.ctypes.data_as(_lib.u32p), out.shape[0], out.shape[1]))
+        return out
+
+    def peak_totals_steps(self):
+        """samples the totals have seen since their last restart"""
+        n = C.c_uint64()
+        self._check(self._L.snn_peak_totals_steps(self._h, C.byref(n)))
+        return int(n.value)
 
     def set_history_stride(self, every):
         self._check(self._L.snn_set_history_stride(self._h, int(every)))
